@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- StofNet hot-path throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5]
+    python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one resident batch of synthetic waveforms per GPU:
@@ -66,6 +66,9 @@ def parse_args(argv=None):
     ap.add_argument('--train-graph', action='store_true',
                     help='C5, fused trainer, one GPU: replay the step from its hipGraph (StofNetTrainer.train_step_graphed) instead of '
                          'launching kernel by kernel; measured equal (r4: 0.805 vs 0.799 ms at batch 4, 4.05 vs 4.04 ms at batch 256)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the timed path returned in its last step (rank 0) as DIR/<name>.npy, '
+                         'float32 or float64, at most 64 MB in all (larger outputs: a fixed, seeded sample of rows)')
     ap.add_argument('--no-extra-configs', action='store_true',
                     help='default run (C2, one GPU): do not measure C3 / C4 / C5 afterwards (extras.configs)')
     ap.add_argument('--dry-run', action='store_true',
@@ -78,6 +81,8 @@ def parse_args(argv=None):
         args.config = 'C5'
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     return args
 
 
@@ -373,6 +378,33 @@ def base_line(args, d, metric, value, dt, dtype, workload, config_extra):
             'config': dict({'workload': workload}, **config_extra)}
 
 
+DUMP_LIMIT = 64_000_000      # bytes over all files of --dump-outputs
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: `arrays` = {name: tensor} that a caller of the timed path received from its last step.  Each goes to
+    <path>/<name>.npy, float64 if it is float64 or integer, else float32.  If they exceed `limit` bytes in all, every array of
+    more than one row keeps the same share of its rows, drawn with a fixed seed (so arrays with the same row count keep the
+    same rows); the row numbers go to <name>_rows.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().to(torch.float64 if v.dtype == torch.float64 or not v.is_floating_point() else torch.float32)
+              for k, v in arrays.items()}
+    header = 256                                                  # bytes of an .npy header, at most
+    rowed = {k for k, t in arrays.items() if t.dim() > 0 and t.shape[0] > 1}
+    fixed = sum(2 * header if k in rowed else t.numel() * t.element_size() + header for k, t in arrays.items())
+    sampled = sum(t.numel() * t.element_size() + 8 * t.shape[0] for k, t in arrays.items() if k in rowed)   # data + row numbers
+    share = 1.0 if fixed + sampled <= limit else max(0, limit - fixed) / sampled
+    for name, t in arrays.items():
+        if share < 1.0 and name in rowed:
+            keep = max(1, int(t.shape[0] * share))
+            rows = np.sort(np.random.default_rng(3008).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(path, f'{name}_rows.npy'), rows.astype(np.float64))
+        np.save(os.path.join(path, f'{name}.npy'), t.cpu().numpy())
+
+
 def dry_run(args):
     """Launcher / process-group rehearsal on the CPU (gloo): the same barrier + max-over-ranks timing and the same
     ragged index gather as the real configs, with a no-op step.  Used by tests/test_bench_launcher.py."""
@@ -424,7 +456,7 @@ def train_bench(args):
     graphed = args.trainer == 'fused' and d.world == 1 and args.train_graph
 
     def step(_s):
-        last['loss'], _ = (tr.train_step_graphed if graphed else tr.train_step)(x, gt)
+        last['loss'], last['pred'] = (tr.train_step_graphed if graphed else tr.train_step)(x, gt)
 
     if args.trainer == 'autograd':
         import torch.nn.functional as F
@@ -447,11 +479,14 @@ def train_bench(args):
                 for prm in model.parameters():
                     allreduce_mean_(prm.grad)
             opt.step()
-            last['loss'] = loss.detach()
+            last['loss'], last['pred'] = loss.detach(), pred.detach()
 
     for s in range(args.warmup):
         step(s)
     dt = d.timed(step, args.steps)
+    if args.dump_outputs and d.rank == 0:           # the step's loss and prediction, and the weights it left behind
+        weights = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        dump_outputs(args.dump_outputs, {'loss': last['loss'], 'pred': last['pred'], 'weights': weights})
     census = d.census()
     d.finish()                                      # all collectives done: rank 0's CPU work below cannot time the group out
     if d.rank == 0:
@@ -674,6 +709,9 @@ def infer_bench(args):
         idx = torch.where(ar < counts[:, None], idx, torch.zeros((), dtype=torch.int32, device=dev)).contiguous()
         extras['picker_argmax_ms'] = round(pick_ms, 3)
         extras['waveforms_per_s_forward_plus_picker'] = round(d.world * rows / (dt / args.steps + pick_ms * 1e-3), 1)
+    if args.dump_outputs and d.rank == 0:
+        # C2 / C3: the maps of the step; C4: the maps of its last chunk and the picks (counts, zero-padded indices) of all chunks
+        dump_outputs(args.dump_outputs, {'maps': y} if cfg != 'C4' else {'maps': y, 'onset_counts': counts, 'onset_indices': idx})
     # the arg-max picker fused into the sweep (stof_forward_onsets): picker-only output, the map never reaches HBM
     if args.precision != 'fp32' and R <= 16:
         def fused_pass():

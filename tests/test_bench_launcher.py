@@ -1,10 +1,13 @@
 """CPU rehearsal of bench.py's multi-rank launch (`python bench.py --gpus N`): the parent spawns N children, rank 0
 prints ONE JSON line with n_gpus = N, the barrier + max-over-ranks timing and the ragged index gather run over gloo.
-No kernels run here (--dry-run); the GPU box runs the same plumbing over RCCL."""
+No kernels run here (--dry-run); the GPU box runs the same plumbing over RCCL.  Also --dump-outputs: its size limit on
+the CPU, and on the GPU that two runs with the same arguments write the same outputs."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 from conftest import ROOT
 
@@ -81,6 +84,63 @@ def test_line_proves_the_ranks_that_took_part(tmp_path):
     ranks = json_lines(p.stdout)[0]['ranks']
     assert ranks['ranks_seen'] == 2 and [r['rank'] for r in ranks['devices']] == [0, 1]
     assert ranks['physical_gpus'] == 0 and 'gloo' in ranks['collective_backend']      # a CPU dry run says so in the record
+
+
+def test_steps_must_be_positive():
+    p = run(['--steps', '0', '--dry-run'])
+    assert p.returncode != 0 and '--steps' in p.stderr
+
+
+def test_dump_outputs_keeps_to_the_size_limit_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: arrays over the limit are cut to the same seeded rows; dtypes are float32 / float64 only."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {'maps': torch.randn(1000, 1, 50, generator=g), 'counts': torch.randint(0, 9, (1000,), generator=g, dtype=torch.int32),
+              'loss': torch.tensor(0.25, dtype=torch.float64)}
+    limit = 60_000
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['counts.npy', 'counts_rows.npy', 'loss.npy', 'maps.npy', 'maps_rows.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= limit
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    rows = np.load(tmp_path / 'a' / 'maps_rows.npy').astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / 'a' / 'counts_rows.npy')) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'maps.npy'), arrays['maps'].numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / 'a' / 'counts.npy'), arrays['counts'].numpy()[rows].astype(np.float64))
+    assert float(np.load(tmp_path / 'a' / 'loss.npy')) == 0.25
+    bench.dump_outputs(str(tmp_path / 'c'), arrays)                  # under the default limit: everything, no row files
+    assert sorted(os.listdir(tmp_path / 'c')) == ['counts.npy', 'loss.npy', 'maps.npy']
+    assert np.array_equal(np.load(tmp_path / 'c' / 'maps.npy'), arrays['maps'].numpy())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('config,rows', [('C2', '64'), ('C4', '1024'), ('C5', '8')])
+def test_dump_outputs_of_two_runs_are_identical(tmp_path, config, rows):
+    """Same arguments, same inputs: two runs of the timed path write the same outputs, and --steps is the timed step count."""
+    import numpy as np
+    recs = []
+    for d in ('a', 'b'):
+        p = run(['--config', config, '--rows', rows, '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-fp32-extra',
+                 '--dump-outputs', str(tmp_path / d)], env={'STOF_BENCH_LOGDIR': str(tmp_path)}, timeout=400)
+        assert p.returncode == 0, p.stderr[-2000:]
+        recs.append(json_lines(p.stdout)[-1])
+    assert all(r['steps'] == 3 and r['ms_per_step'] > 0 for r in recs)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(os.listdir(tmp_path / 'b'))
+    assert files == (['loss.npy', 'pred.npy', 'weights.npy'] if config == 'C5' else
+                     ['maps.npy', 'onset_counts.npy', 'onset_indices.npy'] if config == 'C4' else ['maps.npy'])
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, f
+        if f == 'loss.npy':        # float64 partial sums of the blocks are added atomically, in the order the blocks finish
+            assert np.allclose(a, b, rtol=1e-12, atol=0), (a, b)
+        else:
+            assert np.array_equal(a, b), f
 
 
 def test_under_torch_distributed_run_like_the_driver(tmp_path):

@@ -1135,7 +1135,7 @@ def test_pala_gradpeak_configuration_end_to_end(dev, tmp_path, thn, th):
     assert np.array_equal(pad(es4), pad(want))
 
 
-def test_body_mfma_shape_switch_gives_the_same_maps(dev):
+def test_body_mfma_shape_switch_gives_the_same_maps(dev, tmp_path):
     """STOF_BODY16=0 (read by the packer and the launcher of ONE process) selects the 32x32x16 form of the split-fp16
     body / SemiGlobalBlock kernels kept for A/B runs: same maps within rounding, same onset indices, same golden parity."""
     import subprocess
@@ -1157,7 +1157,7 @@ print('ok', err)
 ''' % (os.path.dirname(os.path.dirname(GOLDEN)), os.path.dirname(GOLDEN))
     outs = []
     for flag in ('1', '0'):
-        path = f'/tmp/stof_body16_{flag}.npy'
+        path = str(tmp_path / f'body16_{flag}.npy')
         env = dict(os.environ, STOF_BODY16=flag)
         p = subprocess.run([sys.executable, '-c', code, path], capture_output=True, text=True, env=env, timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
