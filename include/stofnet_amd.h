@@ -256,6 +256,25 @@ int stof_toa_detect(const float* frame, int64_t N, int64_t L, int32_t grad_step,
 int stof_toa_moments(const float* frame, int64_t N, int64_t L, int32_t grad_step, const float* taps, int32_t radius,
                      float* env_out, double* partials, double* stats, void* stream);
 
+/* GradPeak on float64 envelopes env[N, L] (the envelope of a float64 frame, stof_hilbert_f64): the reference keeps a
+ * float64 input in double at every stage, so these take double taps (models/gradpeak.py:71-76 without the fp32 cast),
+ * a double threshold, and write double echoes / reduced rows; the other arguments and the outputs are those of the fp32
+ * entries above.  Rows need L >= 2 (torch.gradient), else STOF_ERR_UNSUPPORTED.
+ * Pre-pass of the default threshold: adds the sum and the sum of squares of the smoothed gradient to stats[0], stats[1]
+ * (the caller's triple, as for stof_gradpeak_moments) in a fixed order -- the same inputs give the same bits.
+ * workspace: stof_gradpeak_moments_f64_workspace_bytes(N) bytes of device memory (one slot per work-group).          */
+size_t stof_gradpeak_moments_f64_workspace_bytes(int64_t N);
+int stof_gradpeak_moments_f64(const double* env, int64_t N, int64_t L, int32_t grad_step, const double* taps,
+                              int32_t radius, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+/* thres_pos = std**16 * 1.2e13 (:18) in double from stats[3] = (sum, sum of squares, count) into threshold_out[0].     */
+int stof_gradpeak_threshold_f64(const double* stats, double* threshold_out, void* stream);
+/* grad_peak_detect in double: comparisons (> threshold, < -threshold/4) and amplitudes in float64; the positive
+ * threshold is `threshold`, or *threshold_dev when that device pointer is non-NULL (stof_gradpeak_threshold_f64).      */
+int stof_grad_peak_detect_f64(const double* env, int64_t N, int64_t L, int32_t grad_step, const double* taps,
+                              int32_t radius, double threshold, const double* threshold_dev, int32_t ival_min,
+                              int32_t ival_max, int64_t echo_max, double* echoes, int64_t cap, double* reduced,
+                              int32_t* counts, int32_t* flags, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Neighbours of the hot path (SURVEY.md section 8f "next rows").
  * ------------------------------------------------------------------------- */

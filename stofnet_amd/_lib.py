@@ -97,6 +97,13 @@ _SIGNATURES = {
                                    _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     'stof_toa_moments': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32, _c.c_void_p,
                                     _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_gradpeak_moments_f64_workspace_bytes': (_c.c_size_t, [_c.c_int64]),
+    'stof_gradpeak_moments_f64': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32,
+                                             _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_gradpeak_threshold_f64': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_grad_peak_detect_f64': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32,
+                                             _c.c_double, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int64, _c.c_void_p,
+                                             _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     'stof_iq2rf': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _c.c_double,
                               _c.c_int32, _c.c_void_p]),
     'stof_toa_rmse': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_float,

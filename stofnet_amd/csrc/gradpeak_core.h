@@ -58,6 +58,7 @@ struct RowState {
 
 // One word of the pairing: samples base .. base + 63, rising-slope edges EP, falling-slope edges EM (ballot words, so
 // everything here is wave-uniform and runs on the scalar unit).
+// OutT (float or double) is the element type of the echo rows; the pairing itself does not depend on it.
 // Reference (:42-60): every falling-slope edge `am` takes the nearest rising-slope edge `ap` <= am, the gate keeps
 // ival_min < am - ap < ival_max, and per distinct ap the FIRST surviving am is kept.  Read from the ap side: an onset ap
 // owns the stretch [ap, next ap) and its peak is the first EM edge of that stretch inside the gate.  Noisy rows have a
@@ -69,9 +70,9 @@ __device__ __forceinline__ int msb64(unsigned long long v) { return 63 - __built
 // The same pairing for a word crowded with onsets (a threshold near zero makes every noise wiggle an onset): one lane
 // per sample, each falling-slope edge looks up its onset with mask arithmetic and a ballot prefix orders the survivors.
 // Same state as the per-onset form: `done` <=> the last surviving candidate's onset is last_ap.
-template <class EnvAt>
+template <class EnvAt, class OutT>
 __device__ __forceinline__ void pair_word_dense(RowState& st, int base, unsigned long long EP, unsigned long long EM, int lane,
-                                                const Config& cf, float* __restrict__ out, EnvAt env_at) {
+                                                const Config& cf, OutT* __restrict__ out, EnvAt env_at) {
     const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     const unsigned long long le_mask = lt_mask | (1ull << lane);
     const int i = base + lane;
@@ -89,8 +90,8 @@ __device__ __forceinline__ void pair_word_dense(RowState& st, int base, unsigned
     if (keep) {
         const long long pos = st.nout + __builtin_popcountll(km & lt_mask);
         if (pos < cf.cap) {
-            out[3 * pos + 0] = (float)ap;
-            out[3 * pos + 1] = (float)i;
+            out[3 * pos + 0] = (OutT)ap;
+            out[3 * pos + 1] = (OutT)i;
             out[3 * pos + 2] = env_at(i);                      // data[i, am] (:66)
         }
     }
@@ -102,9 +103,9 @@ __device__ __forceinline__ void pair_word_dense(RowState& st, int base, unsigned
     st.done = (last_valid_ap == st.last_ap);
 }
 
-template <class EnvAt>
+template <class EnvAt, class OutT>
 __device__ __forceinline__ void pair_word(RowState& st, int base, unsigned long long EP, unsigned long long EM, int lane,
-                                          const Config& cf, float* __restrict__ out, EnvAt env_at) {
+                                          const Config& cf, OutT* __restrict__ out, EnvAt env_at) {
     st.any_ap |= (EP != 0);
     st.any_am |= (EM != 0);
     if (EP == 0 && (st.last_ap < 0 || st.done)) return;
@@ -129,9 +130,9 @@ __device__ __forceinline__ void pair_word(RowState& st, int base, unsigned long 
                 if (m) {
                     const int am = base + __builtin_ctzll(m);
                     if (st.nout < cf.cap && lane == 0) {
-                        float* o = out + 3ll * st.nout;
-                        o[0] = (float)st.last_ap;
-                        o[1] = (float)am;
+                        OutT* o = out + 3ll * st.nout;
+                        o[0] = (OutT)st.last_ap;
+                        o[1] = (OutT)am;
                         o[2] = env_at(am);                   // data[i, am] (:66)
                     }
                     st.nout += 1;
@@ -464,9 +465,9 @@ __device__ __forceinline__ void stream_blocks(const Config& cf, const float* __r
 // 64 iterations of the pairing at a time: lane l holds the edge words (EP, EM) of the word that iteration c0 + l pairs
 // (= word c0 + l - 1, samples 64 (c0 + l - 1) - rad ...); a ballot tells which iterations hold an onset, and the scalar
 // loop visits only those and the stretch behind a pending onset.
-template <class EnvAt>
+template <class EnvAt, class OutT>
 __device__ __forceinline__ void pair_lane_words(RowState& st, unsigned long long EP, unsigned long long EM, int c0, int lane,
-                                                const Config& cf, float* __restrict__ out, EnvAt env_at) {
+                                                const Config& cf, OutT* __restrict__ out, EnvAt env_at) {
     const int rad = cf.radius;
     {
         const unsigned long long has_ep = __ballot(EP != 0), has_em = __ballot(EM != 0);

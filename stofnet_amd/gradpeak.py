@@ -38,11 +38,12 @@ def gaussian_kernel_1d(sigma: float, num_sigmas: float = 3.) -> torch.Tensor:
 _TAPS = {}
 
 
-def _taps_on(device, grad_step):
-    """Gaussian taps for sigma = (2 g - 1) / 6 as a float32 device tensor (cached per device and step)."""
-    key = (str(device), int(grad_step))
+def _taps_on(device, grad_step, dtype=torch.float32):
+    """Gaussian taps for sigma = (2 g - 1) / 6 as a device tensor of `dtype` (cached per device, step and dtype):
+    gaussian_filter_1d casts them to the data's dtype (models/gradpeak.py:91), so a float64 input keeps them in double."""
+    key = (str(device), int(grad_step), dtype)
     if key not in _TAPS:
-        _TAPS[key] = gaussian_kernel_1d((grad_step * 2 - 1) / 6).to(device, torch.float32)
+        _TAPS[key] = gaussian_kernel_1d((grad_step * 2 - 1) / 6).to(device, dtype)
     return _TAPS[key]
 
 
@@ -67,9 +68,12 @@ def _moment_reduce(stats, group):
 
 def _detect(frame_or_env, is_frame, grad_step, threshold, ival, echo_max, group=None):
     """Shared driver of grad_peak_detect (envelope in) and toa_detect (waveform in): returns what the reference's
-    grad_peak_detect + the echo_max block of toa_detect return.  One host read (flags) per call."""
+    grad_peak_detect + the echo_max block of toa_detect return.  One host read (flags) per call.  A float64 input takes
+    the double-precision path (_detect_f64); every other dtype runs the fp32 kernels."""
     data = frame_or_env
     _lib.require_device(data, 'data')
+    if data.dtype == torch.float64:
+        return _detect_f64(data, is_frame, grad_step, threshold, ival, echo_max, group)
     x = data.detach().contiguous().float()
     n, L = x.shape
     taps = _taps_on(x.device, grad_step)
@@ -135,6 +139,58 @@ def _detect(frame_or_env, is_frame, grad_step, threshold, ival, echo_max, group=
     else:
         out = echoes[:, :kmax]
     return out.to(data.dtype)
+
+
+def _detect_f64(data, is_frame, grad_step, threshold, ival, echo_max, group):
+    """_detect for a float64 frame or envelope: the reference keeps such an input in double at every stage (complex128
+    envelope, gradient, float64 taps, threshold, comparisons, amplitudes), and so does this path: stof_hilbert_f64, then
+    (stof_gradpeak_moments_f64 + stof_gradpeak_threshold_f64 +) stof_grad_peak_detect_f64.  Same cap / re-run protocol and
+    the same one host read as the fp32 path."""
+    x = data.detach().contiguous()
+    n, L = x.shape
+    if n == 0:
+        return torch.zeros((0, 0), dtype=torch.float64, device=x.device)    # no rows: Kmax 0, nothing to launch
+    taps = _taps_on(x.device, grad_step, torch.float64)
+    radius = (taps.numel() - 1) // 2
+    lib = _lib.lib()
+    stream = _lib.stream_ptr(x.device)
+    emax = int(echo_max) if (echo_max is not None and echo_max != float('inf') and echo_max >= 1) else 0
+    th_dev = None
+    with torch.cuda.device(x.device):
+        env = hilbert_envelope(x) if is_frame else x           # float64 in, float64 out (stof_hilbert_f64)
+        if threshold is None:
+            # Q7 in double: (unbiased std of the WHOLE batch tensor) ** 16 * 1.2e13 (models/gradpeak.py:18), on the device
+            stats = torch.tensor([0.0, 0.0, float(n * L)], dtype=torch.float64, device=x.device)
+            ws = torch.empty(max(lib.stof_gradpeak_moments_f64_workspace_bytes(n), 16), dtype=torch.uint8, device=x.device)
+            _lib.check(lib.stof_gradpeak_moments_f64(_lib.ptr(env), n, L, int(grad_step), _lib.ptr(taps), radius, _lib.ptr(stats),
+                                                     _lib.ptr(ws), ws.numel(), stream), 'stof_gradpeak_moments_f64')
+            _moment_reduce(stats, group)
+            th_dev = torch.empty(1, dtype=torch.float64, device=x.device)
+            _lib.check(lib.stof_gradpeak_threshold_f64(_lib.ptr(stats), _lib.ptr(th_dev), stream), 'stof_gradpeak_threshold_f64')
+
+        def run(cap):
+            echoes = torch.empty((n, cap, 3), dtype=torch.float64, device=x.device)
+            reduced = torch.empty((n, emax, 3), dtype=torch.float64, device=x.device) if emax else None
+            counts = torch.empty((n,), dtype=torch.int32, device=x.device)
+            flags = torch.empty((2,), dtype=torch.int32, device=x.device)
+            th = float(threshold) if threshold is not None else 0.0
+            _lib.check(lib.stof_grad_peak_detect_f64(_lib.ptr(env), n, L, int(grad_step), _lib.ptr(taps), radius, th,
+                                                     _lib.ptr(th_dev), ival[0], ival[1], emax, _lib.ptr(echoes), cap,
+                                                     _lib.ptr(reduced), _lib.ptr(counts), _lib.ptr(flags), stream),
+                       'stof_grad_peak_detect_f64')
+            return echoes, reduced, flags
+
+        echoes, reduced, flags = run(_CAP)
+        q9, kmax = (int(v) for v in flags.cpu()) if n else (0, 0)        # the one host read
+        if kmax > _CAP and not q9:
+            echoes, reduced, flags = run(kmax)
+    if q9:
+        return torch.tensor([[], [], []])                               # Q9 (models/gradpeak.py:54-55)
+    if kmax == 0:
+        return torch.zeros((n, 0), dtype=torch.float64, device=x.device)  # (:66, in the input's dtype)
+    if echo_max is not None and kmax > echo_max:                          # toa_detect's reduction (:107-114)
+        return reduced if emax else echoes[:, :0]
+    return echoes[:, :kmax]
 
 
 def grad_peak_detect(data, grad_step: int = None, threshold: float = None, ival_smin: int = None,
