@@ -286,6 +286,32 @@ int stof_grad_peak_detect_f64(const double* env, int64_t N, int64_t L, int32_t g
 int stof_iq2rf(const float* iq, float* rf, int64_t N, int64_t len, double rescale_factor,
                double fc, double fs, int32_t normalize, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Zonzini baselines (models/zonzini.py: ZonziniNetSmall / ZonziniNetLarge), inference in exact fp32.
+ * ------------------------------------------------------------------------- */
+#define STOF_ZONZINI_SMALL 0      /* Conv1d 1->16->32->64->64, fc1 64->1024;   rows need L >= 936   */
+#define STOF_ZONZINI_LARGE 1      /* Conv1d 1->50->100->150->200->250, fc1 250->1024; L >= 3752     */
+typedef struct stof_zonzini_desc {
+    int32_t variant;             /* STOF_ZONZINI_*                                                  */
+    int32_t reserved;            /* 0                                                               */
+} stof_zonzini_desc;
+/* Host-only packer (no HIP call): params = the state_dict's fp32 tensors in module order, conv_layers.{i}.weight,
+ * conv_layers.{i}.bias for every layer, then fc1.weight, fc1.bias, fc2.weight, fc2.bias (12 pointers for Small, 14
+ * for Large).  out: stof_zonzini_packed_bytes(desc) bytes of host memory, copied to the device by the caller.
+ * stof_zonzini_packed_bytes returns 0 for an unknown variant.                                                        */
+size_t stof_zonzini_packed_bytes(const stof_zonzini_desc* desc);
+int stof_zonzini_pack_weights(const stof_zonzini_desc* desc, const float* const* params, void* out, size_t out_bytes);
+/* Device workspace of stof_zonzini_forward for N rows of length L (0 for an unknown variant, N <= 0 or L below the
+ * minimum).  Linear in N up to 256-byte rounding per buffer.                                                         */
+size_t stof_zonzini_workspace_bytes(const stof_zonzini_desc* desc, int64_t N, int64_t L);
+/* x[N, 1, L] fp32 -> y[N, 1] fp32; features (optional, NULL = not written) [N, C_last] = the global average pool's
+ * output.  packed: the packed blob in device memory.  Launches layer 1, one implicit-GEMM kernel per further conv
+ * layer and the head on `stream`; no host sync.  Argument checks come before any HIP call: NULL pointers, N <= 0 or an
+ * unknown variant -> STOF_ERR_BAD_ARG, L below the minimum -> STOF_ERR_POOL_EMPTY (the reference raises in max_pool1d
+ * or in the conv), workspace too small -> STOF_ERR_WORKSPACE.                                                       */
+int stof_zonzini_forward(const stof_zonzini_desc* desc, const float* x, int64_t N, int64_t L, const void* packed,
+                         float* y, float* features, void* workspace, size_t workspace_bytes, void* stream);
+
 /* toa_rmse (utils/metrics.py:9-41): gt[N, G], es[N, E] fp32 with 0/NaN/inf as padding ->
  * out[N, 7] = (rmse, precision, recall, jaccard, tp, fp, fn).                  */
 int stof_toa_rmse(const float* gt, const float* es, int64_t N, int64_t G, int64_t E, float tol,

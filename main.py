@@ -3,7 +3,7 @@
 (reference main.py:29-34,133-177,292-347), running the MI355X-native hot path.
 
 What it keeps: config.yaml + CLI merge, seeding (main.py:39-41), the model switch
-(stofnet / gradpeak, main.py:133-167), checkpoint lookup by file-name prefix with strict
+(stofnet / edsr / espcn / zonzini / gradpeak, main.py:133-167), checkpoint lookup by file-name prefix with strict
 load_state_dict (main.py:173-177), the eval loop's `model(frame)` -> `mask2coords` ->
 `toa_rmse` sequence (main.py:314,320,347), and with `evaluate=False` the training loop
 (main.py:199-289: Gaussian-mask loss, AdamW, CosineAnnealingLR per epoch, EarlyStopping on the
@@ -25,7 +25,7 @@ import torch
 script_path = Path(__file__).parent.resolve()
 sys.path.insert(0, str(script_path))
 
-from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, StofNet, mask2coords          # noqa: E402
+from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, StofNet, ZonziniNetLarge, ZonziniNetSmall, mask2coords  # noqa: E402
 from stofnet_amd import config as config_mod                     # noqa: E402
 from stofnet_amd.metrics import toa_rmse                         # noqa: E402
 
@@ -108,6 +108,9 @@ def main(argv=None):
     elif name == 'espcn':
         model = ESPCN_1D(upscale_factor=cfg.upsample_factor)
         cfg.evaluate = True
+    elif name == 'zonzini':                                               # main.py:135-136: Small on chirp data, else Large
+        model = ZonziniNetSmall() if 'chirp' in str(cfg.data_dir).lower() else ZonziniNetLarge()
+        cfg.evaluate = True                                               # inference only on the gfx950 path
     elif name == 'gradpeak':
         chirp = 'chirp' in str(cfg.data_dir).lower()
         model = GradPeak(threshold=cfg.th, rescale_factor=cfg.rf_scale_factor,

@@ -1,8 +1,9 @@
 """Drop-in for the reference's `models` package (models/__init__.py): `from models import StofNet, ..., GradPeak`
-(main.py:18) resolves unchanged.  StofNet and GradPeak run on the gfx950 kernels (stofnet_amd); EDSR_1D and
-ESPCN_1D ride on the SampleShuffle1D kernel (their convolutions stay stock ATen, as in the reference); the other
-comparison networks of the paper's table are outside the accelerated path and raise when constructed."""
-from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, StofNet  # noqa: F401
+(main.py:18) resolves unchanged.  StofNet, GradPeak and the Zonzini baselines (ZonziniNetSmall / ZonziniNetLarge,
+inference only) run on the gfx950 kernels (stofnet_amd); EDSR_1D and ESPCN_1D ride on the SampleShuffle1D kernel
+(their convolutions stay stock ATen, as in the reference); the other comparison networks of the paper's table
+(SincNet, Kuleshov, WaveUnet) are outside the accelerated path and raise when constructed."""
+from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, StofNet, ZonziniNetLarge, ZonziniNetSmall  # noqa: F401
 from stofnet_amd.stofnet import SemiGlobalBlock  # noqa: F401
 
 
@@ -15,8 +16,6 @@ def _out_of_scope(name):
     return _Baseline
 
 
-ZonziniNetLarge = _out_of_scope('ZonziniNetLarge')
-ZonziniNetSmall = _out_of_scope('ZonziniNetSmall')
 SincNet = _out_of_scope('SincNet')
 Kuleshov = _out_of_scope('Kuleshov')
 WaveUnet = _out_of_scope('WaveUnet')

@@ -7,3 +7,4 @@ from .mask2samples import mask2coords, get_maxima_positions, coords2mask  # noqa
 from .hilbert import hilbert_transform, HilbertTransform  # noqa: F401
 from .gradpeak import GradPeak, toa_detect, grad_peak_detect  # noqa: F401
 from .baselines import EDSR_1D, ESPCN_1D               # noqa: F401
+from .zonzini import ZonziniNetSmall, ZonziniNetLarge  # noqa: F401

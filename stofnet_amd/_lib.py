@@ -33,6 +33,14 @@ class NetDesc(ctypes.Structure):
                 ('precision', ctypes.c_int32), ('seg_policy', ctypes.c_int32)]
 
 
+class ZonziniDesc(ctypes.Structure):
+    _fields_ = [('variant', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+ZONZINI_SMALL = 0
+ZONZINI_LARGE = 1
+
+
 class StofnetLibraryMissing(ImportError):
     pass
 
@@ -104,6 +112,11 @@ _SIGNATURES = {
     'stof_grad_peak_detect_f64': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_int32,
                                              _c.c_double, _c.c_void_p, _c.c_int32, _c.c_int32, _c.c_int64, _c.c_void_p,
                                              _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_zonzini_packed_bytes': (_c.c_size_t, [_c.POINTER(ZonziniDesc)]),
+    'stof_zonzini_pack_weights': (_c.c_int, [_c.POINTER(ZonziniDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
+    'stof_zonzini_workspace_bytes': (_c.c_size_t, [_c.POINTER(ZonziniDesc), _c.c_int64, _c.c_int64]),
+    'stof_zonzini_forward': (_c.c_int, [_c.POINTER(ZonziniDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     'stof_iq2rf': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _c.c_double,
                               _c.c_int32, _c.c_void_p]),
     'stof_toa_rmse': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_float,
