@@ -312,6 +312,41 @@ size_t stof_zonzini_workspace_bytes(const stof_zonzini_desc* desc, int64_t N, in
 int stof_zonzini_forward(const stof_zonzini_desc* desc, const float* x, int64_t N, int64_t L, const void* packed,
                          float* y, float* features, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * SincNet baseline (models/sincnet.py: SincNet with the option dict of main.py:145-157: sinc conv 128 x 1023 taps,
+ * Conv1d 128->128 k 11, 128->128 k 9, 128->1 k 7, each "same" padded + BatchNorm1d (eval) + LeakyReLU(0.2), the
+ * last one linear), inference in exact fp32.  Rows of any length L >= 1.
+ * ------------------------------------------------------------------------- */
+typedef struct stof_sincnet_desc {
+    double fs;                   /* sample rate the sinc layer was built with (SincConv_fast sample_rate), finite, > 0 */
+    double bn_eps;               /* BatchNorm1d eps (1e-5)                                                            */
+    int32_t stop_after;          /* 0 = whole network; 1..3 = run layers 0 .. stop_after - 1 only and leave the last
+                                    one's post-activation output in the workspace (diagnostics; y is not written):
+                                    y may then be NULL.  Buffer (stop_after - 1) & 1 at byte offset 0 or workspace_bytes(desc, N, L) / 2,
+                                    float (8 + n (L + 8) + t) * 128 + c = act[n][c][t]                             */
+    int32_t reserved;            /* 0                                                                                 */
+} stof_sincnet_desc;
+/* Host-only packer (no HIP call): params = 24 host pointers to the state_dict's fp32 tensors in module order,
+ *   [0] conv.0.low_hz_ (128,1)  [1] conv.0.band_hz_ (128,1)
+ *   [2] conv.1.weight (128,128,11) [3] conv.1.bias  [4] conv.2.weight (128,128,9) [5] conv.2.bias
+ *   [6] conv.3.weight (1,128,7)    [7] conv.3.bias
+ *   [8 + 4i .. 11 + 4i] bn.i.weight, bn.i.bias, bn.i.running_mean, bn.i.running_var   (i = 0..3)
+ * The sinc filter bank is synthesised here from low_hz_ / band_hz_ (SincConv_fast.forward, models/sincnet.py:147-188)
+ * in double and rounded to fp32; each BatchNorm (with the conv bias before it) becomes a per-channel affine.
+ * stof_sincnet_packed_bytes returns 0 for a bad desc.                                                                */
+size_t stof_sincnet_packed_bytes(const stof_sincnet_desc* desc);
+int stof_sincnet_pack_weights(const stof_sincnet_desc* desc, const float* const* params, void* out, size_t out_bytes);
+/* The filter bank the packer uses, bank[128][1023] fp32 (host memory; SincConv_fast.filters).                       */
+int stof_sincnet_filter_bank(const stof_sincnet_desc* desc, const float* low_hz, const float* band_hz, float* bank);
+/* Device workspace of stof_sincnet_forward for N rows of length L (0 for a bad desc, N <= 0 or L <= 0): two
+ * channel-last ping-pong buffers of (N (L + 8) + 8) x 128 floats each.                                              */
+size_t stof_sincnet_workspace_bytes(const stof_sincnet_desc* desc, int64_t N, int64_t L);
+/* x[N, 1, L] fp32 -> y[N, 1, L] fp32.  packed: the packed blob in device memory.  Launches 5 kernels on `stream`;
+ * no host sync.  Argument checks come before any HIP call: NULL pointers, N <= 0, L <= 0, fs non-finite or <= 0 ->
+ * STOF_ERR_BAD_ARG, workspace too small -> STOF_ERR_WORKSPACE, N (L + 8) >= 2^31 -> STOF_ERR_UNSUPPORTED.           */
+int stof_sincnet_forward(const stof_sincnet_desc* desc, const float* x, int64_t N, int64_t L, const void* packed,
+                         float* y, void* workspace, size_t workspace_bytes, void* stream);
+
 /* toa_rmse (utils/metrics.py:9-41): gt[N, G], es[N, E] fp32 with 0/NaN/inf as padding ->
  * out[N, 7] = (rmse, precision, recall, jaccard, tp, fp, fn).                  */
 int stof_toa_rmse(const float* gt, const float* es, int64_t N, int64_t G, int64_t E, float tol,

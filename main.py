@@ -3,7 +3,7 @@
 (reference main.py:29-34,133-177,292-347), running the MI355X-native hot path.
 
 What it keeps: config.yaml + CLI merge, seeding (main.py:39-41), the model switch
-(stofnet / edsr / espcn / zonzini / gradpeak, main.py:133-167), checkpoint lookup by file-name prefix with strict
+(stofnet / edsr / espcn / zonzini / sincnet / gradpeak, main.py:133-167), checkpoint lookup by file-name prefix with strict
 load_state_dict (main.py:173-177), the eval loop's `model(frame)` -> `mask2coords` ->
 `toa_rmse` sequence (main.py:314,320,347), and with `evaluate=False` the training loop
 (main.py:199-289: Gaussian-mask loss, AdamW, CosineAnnealingLR per epoch, EarlyStopping on the
@@ -25,7 +25,7 @@ import torch
 script_path = Path(__file__).parent.resolve()
 sys.path.insert(0, str(script_path))
 
-from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, StofNet, ZonziniNetLarge, ZonziniNetSmall, mask2coords  # noqa: E402
+from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, SincNet, StofNet, ZonziniNetLarge, ZonziniNetSmall, mask2coords  # noqa: E402
 from stofnet_amd import config as config_mod                     # noqa: E402
 from stofnet_amd.metrics import toa_rmse                         # noqa: E402
 
@@ -99,6 +99,7 @@ def main(argv=None):
     random.seed(cfg.seed)
     np.random.seed(cfg.seed)
 
+    frames, gt = load_frames(cfg)
     name = str(cfg.model).lower()
     if name == 'stofnet':
         model = StofNet(upsample_factor=cfg.upsample_factor, precision=cfg.precision)
@@ -110,6 +111,19 @@ def main(argv=None):
         cfg.evaluate = True
     elif name == 'zonzini':                                               # main.py:135-136: Small on chirp data, else Large
         model = ZonziniNetSmall() if 'chirp' in str(cfg.data_dir).lower() else ZonziniNetLarge()
+        cfg.evaluate = True                                               # inference only on the gfx950 path
+    elif name == 'sincnet':                                               # main.py:143-158
+        if cfg.fs is None:
+            raise ValueError('model=sincnet needs the sample rate: set the config key fs (Hz of the dataset; the sinc '
+                             'layer is built for fs * rf_scale_factor and the checkpoints do not store it)')
+        cfg.upsample_factor = 1
+        opts = {'input_dim': int(frames.shape[-1]), 'fs': float(cfg.fs) * int(cfg.rf_scale_factor),
+                'cnn_N_filt': [128, 128, 128, 1], 'cnn_len_filt': [1023, 11, 9, 7], 'cnn_max_pool_len': [1, 1, 1, 1],
+                'cnn_use_laynorm_inp': False, 'cnn_use_batchnorm_inp': False,
+                'cnn_use_laynorm': [False, False, False, False], 'cnn_use_batchnorm': [True, True, True, True],
+                'cnn_act': ['leaky_relu', 'leaky_relu', 'leaky_relu', 'linear'], 'cnn_drop': [0.0, 0.0, 0.0, 0.0],
+                'use_sinc': True}
+        model = SincNet(opts)
         cfg.evaluate = True                                               # inference only on the gfx950 path
     elif name == 'gradpeak':
         chirp = 'chirp' in str(cfg.data_dir).lower()
@@ -131,7 +145,6 @@ def main(argv=None):
         if paths:
             model.load_state_dict(torch.load(str(paths[0]), map_location=cfg.device, weights_only=True))
 
-    frames, gt = load_frames(cfg)
     log = RunLog(cfg)
     if log.enabled and str(cfg.run_name) == 'local-run':
         cfg.run_name = log.name                                          # the reference names checkpoints after the wandb run
@@ -255,7 +268,7 @@ def evaluate(model, name, frames, gt, cfg, log=None):
             torch.cuda.synchronize()
             tic = time.perf_counter()
             out = model(frame)
-            if name in ('stofnet', 'edsr', 'espcn'):                     # main.py:318-320
+            if name in ('stofnet', 'edsr', 'espcn', 'sincnet'):          # main.py:318-320
                 es = mask2coords(out, window_size=cfg.nms_win_size, threshold=cfg.th,
                                  upsample_factor=cfg.upsample_factor)
             else:

@@ -1,9 +1,10 @@
 """Drop-in for the reference's `models` package (models/__init__.py): `from models import StofNet, ..., GradPeak`
 (main.py:18) resolves unchanged.  StofNet, GradPeak and the Zonzini baselines (ZonziniNetSmall / ZonziniNetLarge,
 inference only) run on the gfx950 kernels (stofnet_amd); EDSR_1D and ESPCN_1D ride on the SampleShuffle1D kernel
-(their convolutions stay stock ATen, as in the reference); the other comparison networks of the paper's table
-(SincNet, Kuleshov, WaveUnet) are outside the accelerated path and raise when constructed."""
-from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, StofNet, ZonziniNetLarge, ZonziniNetSmall  # noqa: F401
+(their convolutions stay stock ATen, as in the reference); SincNet runs on the gfx950 kernels for the option dict of
+main.py (inference only; SincNet() without options raises NotImplementedError); the other comparison networks of the
+paper's table (Kuleshov, WaveUnet) are outside the accelerated path and raise when constructed."""
+from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, SincNet, StofNet, ZonziniNetLarge, ZonziniNetSmall  # noqa: F401
 from stofnet_amd.stofnet import SemiGlobalBlock  # noqa: F401
 
 
@@ -16,6 +17,5 @@ def _out_of_scope(name):
     return _Baseline
 
 
-SincNet = _out_of_scope('SincNet')
 Kuleshov = _out_of_scope('Kuleshov')
 WaveUnet = _out_of_scope('WaveUnet')

@@ -41,6 +41,11 @@ ZONZINI_SMALL = 0
 ZONZINI_LARGE = 1
 
 
+class SincNetDesc(ctypes.Structure):
+    _fields_ = [('fs', ctypes.c_double), ('bn_eps', ctypes.c_double), ('stop_after', ctypes.c_int32),
+                ('reserved', ctypes.c_int32)]
+
+
 class StofnetLibraryMissing(ImportError):
     pass
 
@@ -117,6 +122,12 @@ _SIGNATURES = {
     'stof_zonzini_workspace_bytes': (_c.c_size_t, [_c.POINTER(ZonziniDesc), _c.c_int64, _c.c_int64]),
     'stof_zonzini_forward': (_c.c_int, [_c.POINTER(ZonziniDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
                                         _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_sincnet_packed_bytes': (_c.c_size_t, [_c.POINTER(SincNetDesc)]),
+    'stof_sincnet_pack_weights': (_c.c_int, [_c.POINTER(SincNetDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
+    'stof_sincnet_filter_bank': (_c.c_int, [_c.POINTER(SincNetDesc), _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_sincnet_workspace_bytes': (_c.c_size_t, [_c.POINTER(SincNetDesc), _c.c_int64, _c.c_int64]),
+    'stof_sincnet_forward': (_c.c_int, [_c.POINTER(SincNetDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     'stof_iq2rf': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _c.c_double,
                               _c.c_int32, _c.c_void_p]),
     'stof_toa_rmse': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_float,

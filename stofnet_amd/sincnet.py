@@ -1,0 +1,268 @@
+"""The SincNet baseline of the reference (models/sincnet.py: SincNet with the option dict of main.py:145-157) on the
+gfx950 kernels of csrc/sincnet.hip, inference only, exact fp32.
+
+The module tree (`conv`, `bn`, `ln`, `act`, `drop`), parameter names, shapes and default initialisation are the
+reference's, so its checkpoints load with strict=True.  The layers are parameter holders: the forward never calls their
+ATen kernels.  It packs the parameters (and the BatchNorm running statistics) once per change, synthesising the sinc
+filter bank on the host, splits the batch into chunks whose workspace stays under `max_workspace_bytes`, and launches
+the HIP forward on the current stream.  Rows are bitwise independent of the batch they sit in, so the chunking does not
+show in the result.
+
+Only the configuration the shipped checkpoints were trained with is accelerated (`ACCELERATED_OPTIONS`, any
+`input_dim`, any `cnn_drop`, `fs` > 0); any other option dict raises NotImplementedError naming the key."""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+N_FILT = 128
+SINC_TAPS = 1023
+MIN_LOW_HZ = 50.0
+MIN_BAND_HZ = 50.0
+GAP = 8                                     # zero rows around every waveform in the workspace (csrc/sincnet.hip)
+
+# main.py:145-157 without input_dim, fs and cnn_drop
+ACCELERATED_OPTIONS = {
+    'cnn_N_filt': [128, 128, 128, 1],
+    'cnn_len_filt': [1023, 11, 9, 7],
+    'cnn_max_pool_len': [1, 1, 1, 1],
+    'cnn_use_laynorm_inp': False,
+    'cnn_use_batchnorm_inp': False,
+    'cnn_use_laynorm': [False, False, False, False],
+    'cnn_use_batchnorm': [True, True, True, True],
+    'cnn_act': ['leaky_relu', 'leaky_relu', 'leaky_relu', 'linear'],
+    'use_sinc': True,
+}
+
+
+def _same(a, b):
+    if isinstance(b, list):
+        return isinstance(a, (list, tuple)) and len(a) == len(b) and all(_same(u, v) for u, v in zip(a, b))
+    if isinstance(b, bool):
+        return isinstance(a, (bool, np.bool_)) and bool(a) == b
+    if isinstance(b, str):
+        return a == b
+    return not isinstance(a, (bool, np.bool_)) and isinstance(a, (int, float, np.integer, np.floating)) and a == b
+
+
+def check_options(options):
+    """Raise NotImplementedError naming the first key of `options` outside the accelerated configuration."""
+    if not isinstance(options, dict):
+        raise NotImplementedError('SincNet needs the option dict of main.py (the gfx950 path accelerates exactly that '
+                                  'configuration)')
+    for key, want in ACCELERATED_OPTIONS.items():
+        if key not in options:
+            raise NotImplementedError(f'SincNet: option {key!r} is missing')
+        if not _same(options[key], want):
+            raise NotImplementedError(f'SincNet: option {key}={options[key]!r} is not supported on the gfx950 path '
+                                      f'(supported: {want!r})')
+    for key in ('input_dim', 'fs', 'cnn_drop'):
+        if key not in options:
+            raise NotImplementedError(f'SincNet: option {key!r} is missing')
+    try:
+        fs = float(options['fs'])
+    except (TypeError, ValueError):
+        raise NotImplementedError(f"SincNet: option fs={options['fs']!r} is not a sample rate") from None
+    if not (math.isfinite(fs) and fs > 0):
+        raise NotImplementedError(f'SincNet: option fs={fs!r} is not supported (needs a finite sample rate > 0)')
+    drop = options['cnn_drop']
+    if not isinstance(drop, (list, tuple)) or len(drop) != 4:
+        raise NotImplementedError(f'SincNet: option cnn_drop={drop!r} is not supported (needs 4 dropout rates)')
+
+
+def mel_init(fs, n_filt=N_FILT):
+    """SincConv_fast's default bands for sample rate fs: n_filt + 1 edges equally spaced in mel between 30 Hz and
+    fs / 2 - 100 Hz -> (low_hz_, band_hz_) as float32 [n_filt, 1]."""
+    to_mel = lambda hz: 2595 * np.log10(1 + hz / 700)            # noqa: E731
+    to_hz = lambda mel: 700 * (10 ** (mel / 2595) - 1)           # noqa: E731
+    edges = to_hz(np.linspace(to_mel(30), to_mel(fs / 2 - (MIN_LOW_HZ + MIN_BAND_HZ)), n_filt + 1))
+    return (torch.tensor(edges[:-1], dtype=torch.float32).view(-1, 1),
+            torch.tensor(np.diff(edges), dtype=torch.float32).view(-1, 1))
+
+
+def filter_bank(fs, low_hz, band_hz):
+    """The sinc filter bank of the packer (SincConv_fast.filters, synthesised in double) -> float32 [128, 1, 1023]."""
+    lib = _lib.lib()
+    desc = _lib.SincNetDesc(float(fs), 1e-5, 0, 0)
+    lo = np.ascontiguousarray(np.asarray(low_hz, np.float32).reshape(-1))
+    bd = np.ascontiguousarray(np.asarray(band_hz, np.float32).reshape(-1))
+    if lo.size != N_FILT or bd.size != N_FILT:
+        raise ValueError(f'low_hz / band_hz need {N_FILT} entries')
+    bank = np.zeros((N_FILT, SINC_TAPS), np.float32)
+    _lib.check(lib.stof_sincnet_filter_bank(ctypes.byref(desc), lo.ctypes.data, bd.ctypes.data, bank.ctypes.data),
+               'stof_sincnet_filter_bank')
+    return torch.from_numpy(bank).view(N_FILT, 1, SINC_TAPS)
+
+
+class SincConv(nn.Module):
+    """Parameter holder of SincConv_fast (models/sincnet.py:58-188) for 128 filters of 1023 taps: `low_hz_`,
+    `band_hz_` [128, 1] with the mel-spaced default for `sample_rate`.  `filters` is the bank the kernels use."""
+
+    def __init__(self, out_channels, kernel_size, sample_rate):
+        super().__init__()
+        self.out_channels = out_channels
+        self.kernel_size = kernel_size
+        self.sample_rate = sample_rate
+        self.min_low_hz = MIN_LOW_HZ
+        self.min_band_hz = MIN_BAND_HZ
+        low, band = mel_init(sample_rate, out_channels)
+        self.low_hz_ = nn.Parameter(low)
+        self.band_hz_ = nn.Parameter(band)
+
+    @property
+    def filters(self):
+        return filter_bank(self.sample_rate, self.low_hz_.detach().cpu().numpy(), self.band_hz_.detach().cpu().numpy())
+
+
+class SincNet(nn.Module):
+    """models/sincnet.py SincNet(options) for the option dict of main.py:145-157: sinc conv 1 -> 128 (1023 taps), Conv1d
+    128 -> 128 (k 11), 128 -> 128 (k 9), 128 -> 1 (k 7), each "same" zero padded, followed by BatchNorm1d (eval) and
+    LeakyReLU(0.2) (the last one linear).  x [N, L] or [N, 1, L] float32 -> y [N, 1, L]."""
+    max_workspace_bytes = 512 << 20
+
+    def __init__(self, options=None):
+        super().__init__()
+        check_options(options)
+        self.cnn_N_filt = list(options['cnn_N_filt'])
+        self.cnn_len_filt = list(options['cnn_len_filt'])
+        self.cnn_max_pool_len = list(options['cnn_max_pool_len'])
+        self.cnn_act = list(options['cnn_act'])
+        self.cnn_drop = list(options['cnn_drop'])
+        self.cnn_use_laynorm = list(options['cnn_use_laynorm'])
+        self.cnn_use_batchnorm = list(options['cnn_use_batchnorm'])
+        self.cnn_use_laynorm_inp = options['cnn_use_laynorm_inp']
+        self.cnn_use_batchnorm_inp = options['cnn_use_batchnorm_inp']
+        self.input_dim = int(options['input_dim'])
+        self.fs = options['fs']
+        self.use_sinc = options['use_sinc']
+        self.N_cnn_lay = 4
+        self.conv = nn.ModuleList()
+        self.bn = nn.ModuleList()
+        self.ln = nn.ModuleList()                # empty, as in the reference (no layer norm in this configuration)
+        self.act = nn.ModuleList()
+        self.drop = nn.ModuleList()
+        cur = self.input_dim
+        for i in range(4):                        # the reference's construction order (torch's RNG draws match)
+            self.drop.append(nn.Dropout(p=self.cnn_drop[i]))
+            self.act.append(nn.LeakyReLU(0.2) if self.cnn_act[i] == 'leaky_relu' else nn.LeakyReLU(1))
+            self.bn.append(nn.BatchNorm1d(self.cnn_N_filt[i], momentum=0.05))
+            if i == 0:
+                self.conv.append(SincConv(self.cnn_N_filt[0], self.cnn_len_filt[0], self.fs))
+            else:
+                self.conv.append(nn.Conv1d(self.cnn_N_filt[i - 1], self.cnn_N_filt[i], self.cnn_len_filt[i]))
+            cur = int((cur - self.cnn_len_filt[i] + 1) / self.cnn_max_pool_len[i])
+        self.out_dim = cur * self.cnn_N_filt[-1]
+        self._packed = None
+        self._packed_key = None
+
+    def _desc(self, stop_after=0):
+        eps = {float(b.eps) for b in self.bn}
+        if len(eps) != 1:
+            raise NotImplementedError('SincNet: the BatchNorm layers must share one eps on the gfx950 path')
+        return _lib.SincNetDesc(float(self.fs), eps.pop(), int(stop_after), 0)
+
+    def _params(self):
+        ps = [self.conv[0].low_hz_, self.conv[0].band_hz_]
+        for conv in self.conv[1:]:
+            ps += [conv.weight, conv.bias]
+        for bn in self.bn:
+            ps += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        return ps
+
+    def invalidate_packed(self):
+        """Drop the packed weights (they are rebuilt on the next forward; parameter edits are also detected on their own)."""
+        self._packed = None
+        self._packed_key = None
+
+    def packed_weights(self, device):
+        params = self._params()
+        for p in params:
+            if p.dtype != torch.float32:
+                raise TypeError(f'SincNet: parameters and BatchNorm statistics must be float32 (got {p.dtype}); the '
+                                'gfx950 kernels are fp32 only')
+        desc = self._desc()
+        key = (str(device), desc.fs, desc.bn_eps) + tuple((p.data_ptr(), p._version) for p in params)
+        if self._packed is None or self._packed_key != key:
+            host = [np.ascontiguousarray(p.detach().cpu().numpy(), dtype=np.float32) for p in params]
+            self._packed = pack_weights(desc.fs, host, desc.bn_eps).to(device)
+            self._packed_key = key
+        return self._packed
+
+    def _check_input(self, x):
+        if self.training:
+            raise NotImplementedError('SincNet: training is not implemented on the gfx950 path (in train mode the '
+                                      "reference's BatchNorm uses batch statistics, also under no_grad; call model.eval())")
+        _lib.require_device(x, 'x')
+        if x.dtype != torch.float32:
+            raise TypeError(f'SincNet: x must be float32 (got {x.dtype}); the gfx950 kernels are fp32 only')
+        if not (x.dim() == 2 or (x.dim() == 3 and x.shape[1] == 1)):
+            raise RuntimeError(f'SincNet: expected x of shape [N, L] or [N, 1, L], got {list(x.shape)}')
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError('SincNet: backward is not implemented on the gfx950 path (inference only: run '
+                                      'under torch.no_grad() or detach the input)')
+        if int(x.shape[-1]) < 1:
+            raise RuntimeError('SincNet: rows must hold at least one sample')
+
+    def forward(self, x):
+        self._check_input(x)
+        N, L = int(x.shape[0]), int(x.shape[-1])
+        y = torch.empty((N, 1, L), dtype=torch.float32, device=x.device)
+        if N == 0:
+            return y
+        self._launch(x, y, 0)
+        return y
+
+    def forward_layers(self, x):
+        """The post-activation outputs of layers 0, 1 and 2 (the reference's `act[i]` outputs), each [N, 128, L]
+        float32: three forwards that stop after the layer, read back from the workspace.  Diagnostics only."""
+        self._check_input(x)
+        N, L = int(x.shape[0]), int(x.shape[-1])
+        outs = []
+        for k in (1, 2, 3):
+            ws, half = self._launch(x, None, k, chunked=False)
+            buf = ws[((k - 1) & 1) * half:].view(torch.float32)[GAP * N_FILT:GAP * N_FILT + N * (L + GAP) * N_FILT]
+            outs.append(buf.view(N, L + GAP, N_FILT)[:, :L, :].permute(0, 2, 1).contiguous())
+        return outs
+
+    def _launch(self, x, y, stop_after, chunked=True):
+        N, L = int(x.shape[0]), int(x.shape[-1])
+        x = x.detach().reshape(N, L).contiguous()
+        packed = self.packed_weights(x.device)
+        lib = _lib.lib()
+        desc = self._desc(stop_after)
+        per_row = int(lib.stof_sincnet_workspace_bytes(ctypes.byref(desc), 1, L))
+        chunk = max(1, min(N, int(self.max_workspace_bytes) // per_row)) if chunked else N
+        ws_bytes = int(lib.stof_sincnet_workspace_bytes(ctypes.byref(desc), chunk, L))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        stream = _lib.stream_ptr(x.device)
+        for r0 in range(0, N, chunk):
+            n = min(chunk, N - r0)
+            _lib.check(lib.stof_sincnet_forward(
+                ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), n, L, _lib.ptr(packed),
+                None if y is None else ctypes.c_void_p(y[r0].data_ptr()), _lib.ptr(ws), ws_bytes, stream),
+                'stof_sincnet_forward')
+        return ws, ws_bytes // 2
+
+
+def pack_weights(fs, params, bn_eps=1e-5):
+    """Host-side packing (stof_sincnet_pack_weights) of the 24 float32 arrays in module order (see the header) -> a
+    uint8 CPU tensor holding the blob."""
+    lib = _lib.lib()
+    desc = _lib.SincNetDesc(float(fs), float(bn_eps), 0, 0)
+    n = int(lib.stof_sincnet_packed_bytes(ctypes.byref(desc)))
+    if n == 0:
+        raise ValueError(f'bad SincNet description (fs={fs!r}, bn_eps={bn_eps!r})')
+    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in params]
+    if len(arrs) != 24:
+        raise ValueError(f'SincNet packing needs 24 arrays, got {len(arrs)}')
+    ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    blob = torch.zeros(n, dtype=torch.uint8)
+    _lib.check(lib.stof_sincnet_pack_weights(ctypes.byref(desc), ptrs, ctypes.c_void_p(blob.data_ptr()), n),
+               'stof_sincnet_pack_weights')
+    return blob
