@@ -144,7 +144,9 @@ int stof_event_elapsed_ms(void* start, void* stop, float* ms_out);
 int stof_sample_shuffle(const float* in, float* out, int64_t N, int64_t C_in,
                         int64_t W, int32_t r, void* stream);
 /* The same permutation for elements of elem_bytes = 1, 2, 4, 8 or 16 bytes, bit for bit: the reference's
- * view / permute / contiguous (utils/sample_shuffle.py:24-27) is dtype-agnostic (int64 ramps, float64, float16, complex). */
+ * view / permute / contiguous (utils/sample_shuffle.py:24-27) is dtype-agnostic (int64 ramps, float64, float16, complex).
+ * Any r >= 1: an LDS-tiled kernel while its [r][257] tile fits in 64 KiB (r * 257 * elem_bytes), a plain gather kernel
+ * beyond.  STOF_ERR_UNSUPPORTED only when the grid would exceed 2^31 - 1 work-groups. */
 int stof_sample_shuffle_bytes(const void* in, void* out, int64_t N, int64_t C_in,
                               int64_t W, int32_t r, int32_t elem_bytes, void* stream);
 

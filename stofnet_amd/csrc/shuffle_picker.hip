@@ -58,6 +58,21 @@ __global__ __launch_bounds__(256) void sample_shuffle_kernel(const T* __restrict
 }
 struct alignas(16) shuf_u128 { unsigned long long lo, hi; };
 
+// The same permutation as a plain gather, for the shapes whose [r][TW + 1] tile would not fit in 64 KiB of LDS (large r or
+// wide elements): one output element per thread, so the writes are coalesced and the reads stride by C*W; 64-bit indices.
+template <typename T>
+__global__ __launch_bounds__(256) void sample_shuffle_gather_kernel(const T* __restrict__ in, T* __restrict__ out, long long C,
+                                                                    long long W, long long r, long long total) {
+    const long long i = blockIdx.x * 256ll + threadIdx.x;
+    if (i >= total) return;
+    const long long Wr = W * r;
+    const long long nc = i / Wr;                   // n * C + c
+    const long long j = i - nc * Wr;               // w * r + k
+    const long long w = j / r, k = j - w * r;
+    const long long n = nc / C, c = nc - n * C;
+    out[i] = in[((n * r + k) * C + c) * W + w];
+}
+
 // ----------------------------------------------------------------------------------
 // pick_maxima: one work-group per row.  A sample is a detection iff
 //      s == max(window)  &&  s != 0  &&  s >= cut
@@ -379,9 +394,20 @@ extern "C" int stof_reduce_echoes(const float* scores, int64_t N, int64_t M, con
 }
 
 namespace {
+constexpr int64_t SHUF_TILE_MAX_BYTES = 64 * 1024;      // the LDS-tile kernel runs without raising the dynamic-LDS limit
+
 template <typename T>
 int launch_shuffle(const void* in, void* out, int64_t N, int64_t C_in, int64_t W, int32_t r, void* stream) {
     const int64_t C = C_in / r;
+    if ((int64_t)r * (SHUF_TW + 1) * (int64_t)sizeof(T) > SHUF_TILE_MAX_BYTES || C > 0x7fffffffLL || W > 0x7fffffffLL) {
+        const int64_t total = N * C_in * W;
+        const int64_t blocks = (total + 255) / 256;
+        if (blocks > 0x7fffffffLL) return STOF_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(sample_shuffle_gather_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           static_cast<const T*>(in), static_cast<T*>(out), (long long)C, (long long)W, (long long)r,
+                           (long long)total);
+        return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP;
+    }
     const int64_t tiles_w = (W + SHUF_TW - 1) / SHUF_TW;
     const int64_t blocks = N * C * tiles_w;
     if (blocks > 0x7fffffffLL) return STOF_ERR_UNSUPPORTED;
@@ -398,7 +424,6 @@ extern "C" int stof_sample_shuffle_bytes(const void* in, void* out, int64_t N, i
     if (C_in % r != 0) return STOF_ERR_CHANNELS;
     if (N == 0 || C_in == 0 || W == 0) return STOF_OK;
     if (!in || !out) return STOF_ERR_BAD_ARG;
-    if (r > 128 || (elem_bytes == 16 && r > 32)) return STOF_ERR_UNSUPPORTED;      // the [r][257] LDS tile
     switch (elem_bytes) {
     case 1: return launch_shuffle<unsigned char>(in, out, N, C_in, W, r, stream);
     case 2: return launch_shuffle<unsigned short>(in, out, N, C_in, W, r, stream);

@@ -985,7 +985,8 @@ def test_forward_onsets_matches_forward_plus_picker_on_golden(dev, precision):
     assert torch.equal(c3, counts) and torch.equal(i3, idx)
 
 
-@pytest.mark.parametrize('r,L,n', [(4, 2000, 300), (10, 2000, 64), (16, 1536, 33), (1, 400, 5), (4, 96, 7), (10, 2000, 3), (4, 1536, 4100)])
+@pytest.mark.parametrize('r,L,n', [(4, 2000, 300), (10, 2000, 64), (16, 1536, 33), (1, 400, 5), (4, 96, 7), (10, 2000, 3), (4, 1536, 4100),
+                                   (2, 400, 5), (3, 2000, 64), (5, 1536, 33), (13, 400, 7), (15, 2000, 3)])
 def test_forward_onsets_shapes_batches_segments(dev, r, L, n):
     """Row lengths that are no multiple of the 16-row tiles, waveform boundaries inside tiles, small batches (segment
     mode), several sub-batches, r that is no multiple of 4: always the same indices as the map + picker kernel."""
@@ -1031,11 +1032,15 @@ def test_forward_onsets_ties_and_degenerate_rows(dev):
 def test_forward_onsets_falls_back_outside_the_fused_tile(dev):
     from stofnet_amd.mask2samples import onset_indices
     x = torch.from_numpy(synth.synth_echo(5, 400, seed=4)).to(dev)
-    for r, precision in ((20, 'auto'), (4, 'fp32')):
+    for r, precision in ((20, 'auto'), (4, 'fp32'), (17, 'auto'), (64, 'auto')):
         m = make_model(dev, synth.synth_state_dict(r, seed=9), r, precision=precision)
         counts, idx = m.forward_onsets(x, 20)
         c2, i2 = onset_indices(m(x), 20, None)
         assert torch.equal(counts, c2) and torch.equal(idx, i2)
+        if r in (17, 64):
+            ref = po.maxima_positions(so.stofnet_forward(synth.synth_state_dict(r, seed=9), x[:2].cpu().numpy(), r, 80).numpy(), 20, None)
+            got = [(row, int(t)) for row in range(2) for t in idx[row, :int(counts[row])].cpu().numpy()]
+            assert got == [tuple(v) for v in ref.tolist()]
     m = make_model(dev, synth.synth_state_dict(4, seed=12), 4, precision='auto')
     big = x * 3.0e6                                          # fp16 range overflow: exact-fp32 map path
     counts, idx = m.forward_onsets(big, 20)

@@ -139,7 +139,9 @@ def test_conv_last_data_gradient_kernel(dev, r, n, L):
 
 
 @pytest.mark.parametrize('precision', ['fp32', 'f16x3'])
-@pytest.mark.parametrize('r,sgs,L', [(4, 80, 400), (10, 80, 336), (4, 1, 250)])
+@pytest.mark.parametrize('r,sgs,L', [(4, 80, 400), (10, 80, 336), (4, 1, 250),
+                                     # r without a dedicated conv_last data-gradient kernel; onsets at both row ends
+                                     (1, 80, 400), (3, 80, 400), (17, 80, 400), (33, 80, 400), (64, 80, 400), (17, 1, 400)])
 def test_loss_and_all_gradients_vs_autograd(dev, r, sgs, L, precision):
     sd, m, tr = make(dev, r, sgs, precision=precision)
     n = 3
@@ -147,6 +149,8 @@ def test_loss_and_all_gradients_vs_autograd(dev, r, sgs, L, precision):
     rng = np.random.default_rng(5)
     gt = np.stack([np.sort(rng.integers(1, L * r, size=2)) for _ in range(n)])[:, None, :].astype(np.int64)
     gt[1, 0, 1] = 0                                                        # "no echo" placeholder (index 0 is cleared)
+    if r not in (4, 10):
+        gt[0, 0, 0], gt[2, 0, 1] = 1, L * r - 1                            # the 7-tap target blur clipped at both row ends
     loss_ref, grads_ref, pred_ref = to.loss_and_grads(sd, x, gt, r, sgs)
     loss, pred = tr.forward_backward(torch.from_numpy(x).to(dev), torch.from_numpy(gt).to(dev))
     assert relerr(pred.cpu().numpy(), pred_ref) < 1e-5
