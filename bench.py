@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- StofNet hot-path throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--config C2|C3|C4|C5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one resident batch of synthetic waveforms per GPU:
@@ -22,8 +22,11 @@ rendezvous on 127.0.0.1) and relays rank 0's line -- it never touches the GPU it
 ranks come from the environment and --gpus must agree with WORLD_SIZE.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant kernel (body sweep,
-MFMA-bound, timed with HIP events on its launch stream inside the timed region) and `cpu_baseline` (the CPU oracle =
-PyTorch-CPU restatement, timed on this box's host cores, N = 1 only).
+MFMA-bound, timed with HIP events on its launch stream inside the timed region).  A plain run does only what that line
+needs: set-up, warm-up, the timed steps, --dump-outputs.  --full also measures and checks everything else after the timed
+region: `cpu_baseline` (the CPU oracle = PyTorch-CPU restatement, timed on this box's host cores, with the parity of the
+timed outputs, N = 1 only), the pickers, the fused onsets, the exact-fp32 mode, the onset gather over the ranks, the
+recorded HBM traffic, and, on the default C2 run, the other configs under `extras.configs`.
 """
 import argparse
 import json
@@ -51,8 +54,11 @@ def parse_args(argv=None):
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', default='C2', choices=['C2', 'C3', 'C4', 'C5'])
     ap.add_argument('--precision', default=os.environ.get('STOF_PRECISION', 'auto'), choices=['auto', 'fp32', 'f16x3'])
-    ap.add_argument('--no-fp32-extra', action='store_true', help='skip the secondary exact-fp32 measurement')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure and check what the headline figure does not need (CPU baseline '
+                         'and parity, pickers, fused onsets, exact-fp32 mode, onset gather, recorded traffic, extras.configs)')
+    ap.add_argument('--no-fp32-extra', action='store_true', help='--full: skip the secondary exact-fp32 measurement')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline and its parity check')
     ap.add_argument('--mode', default='infer', choices=['infer', 'train'], help="'train' = --config C5")
     ap.add_argument('--train-batch', type=int, default=256, help='waveforms per GPU per training step')
     ap.add_argument('--train-precision', default='f16x3', choices=['fp32', 'f16x3'],
@@ -62,7 +68,7 @@ def parse_args(argv=None):
                          "torch.optim.AdamW lines on the module's autograd boundary (main.py:221-248)")
     ap.add_argument('--rows', type=int, default=0, help='override the rows per GPU of the chosen config (smoke runs)')
     ap.add_argument('--cpu-sample-rows', type=int, default=0,
-                    help='rows of the bounded CPU-oracle sample (default: 256; C4 128; the extra configs of the default run use 32)')
+                    help='--full: rows of the bounded CPU-oracle sample (default: 256; C4 128; the extra configs use 32)')
     ap.add_argument('--train-graph', action='store_true',
                     help='C5, fused trainer, one GPU: replay the step from its hipGraph (StofNetTrainer.train_step_graphed) instead of '
                          'launching kernel by kernel; measured equal (r4: 0.805 vs 0.799 ms at batch 4, 4.05 vs 4.04 ms at batch 256)')
@@ -70,7 +76,7 @@ def parse_args(argv=None):
                     help='after the timed steps, write what the timed path returned in its last step (rank 0) as DIR/<name>.npy, '
                          'float32 or float64, at most 64 MB in all (larger outputs: a fixed, seeded sample of rows)')
     ap.add_argument('--no-extra-configs', action='store_true',
-                    help='default run (C2, one GPU): do not measure C3 / C4 / C5 afterwards (extras.configs)')
+                    help='--full on the default run (C2, one GPU): do not measure C3 / C4 / C5 afterwards (extras.configs)')
     ap.add_argument('--dry-run', action='store_true',
                     help='rehearse the launcher and the distributed plumbing on the CPU (gloo, no kernels): tests only')
     ap.add_argument('--rehearse-on-one-gpu', action='store_true',
@@ -514,7 +520,7 @@ def train_bench(args):
                            'sparse_sgb_backward_taken': sparse_sgb}
         out['final_loss'] = float(last['loss'])
         out['ranks'] = census
-        if not args.no_cpu_baseline and d.world == 1:       # rank 0 at N = 1 only (the process group is already closed)
+        if args.full and not args.no_cpu_baseline and d.world == 1:   # rank 0 at N = 1 only (the process group is already closed)
             # the oracle's training step (torch autograd on the host cores), bounded sample
             from oracle import train_oracle
             cores = host_cores()
@@ -552,7 +558,7 @@ def run_extra_configs(args):
             ('C5_batch4', ['--config', 'C5', '--steps', '50', '--warmup', '5', '--rows', '4'])]
     out = {}
     for name, extra in runs:
-        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--no-extra-configs', '--no-fp32-extra',
+        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--full', '--no-extra-configs', '--no-fp32-extra',
                '--cpu-sample-rows', '32', '--precision', args.precision, '--train-precision', args.train_precision] + extra
         t0 = time.perf_counter()
         try:
@@ -678,7 +684,7 @@ def infer_bench(args):
         lib.stof_events_destroy(nev, arr)
     k_ms = kern.mean(0)
 
-    # extras outside the timed region: picker and optional RCCL gather of the onset indices
+    # extras outside the timed region (--full): picker and optional RCCL gather of the onset indices
     extras = {}
     if cfg == 'C4':
         kmax = int(counts_all.max())
@@ -687,6 +693,7 @@ def infer_bench(args):
         counts = counts_all
         ar = torch.arange(max(kmax, 1), device=dev)[None, :]
         idx = torch.where(ar < counts[:, None], idx_all[:, :max(kmax, 1)], torch.zeros((), dtype=torch.int32, device=dev)).contiguous()
+    if cfg == 'C4' and args.full:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for c in range(nchunk):
@@ -697,7 +704,7 @@ def infer_bench(args):
         extras['picker_threshold_ms_per_step'] = round(dt / args.steps * 1e3 - fwd_only * 1e3, 3)
         extras['detections_per_row_mean'] = round(float(counts.float().mean()), 3)
         extras['kmax'] = kmax
-    else:
+    elif args.full:
         counts, idx = onset_indices(y, 20, None)          # warm-up: first use loads the picker's code object
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -713,7 +720,7 @@ def infer_bench(args):
         # C2 / C3: the maps of the step; C4: the maps of its last chunk and the picks (counts, zero-padded indices) of all chunks
         dump_outputs(args.dump_outputs, {'maps': y} if cfg != 'C4' else {'maps': y, 'onset_counts': counts, 'onset_indices': idx})
     # the arg-max picker fused into the sweep (stof_forward_onsets): picker-only output, the map never reaches HBM
-    if args.precision != 'fp32' and R <= 16:
+    if args.full and args.precision != 'fp32' and R <= 16:
         def fused_pass():
             for c in range(nchunk):
                 model.forward_onsets(x if nchunk == 1 else x[c * chunk:(c + 1) * chunk], 20)
@@ -751,20 +758,21 @@ def infer_bench(args):
                                          'note': 'StofNet.forward_onsets(sync=False): output = onset indices only, counts and the '
                                                  'range-guard word read once after the timed loop; the *_with_host_sync figures '
                                                  'include the per-call Kmax read the reference has (utils/mask2samples.py:93)'}
-    extras['index_gather_ms'] = None
-    if d.dist is not None:
-        gather_onsets(counts, idx)                       # warm-up (communicator set-up)
-        torch.cuda.synchronize()
-        d.barrier()
-        t1 = time.perf_counter()
-        c_all, i_all = gather_onsets(counts, idx)
-        torch.cuda.synchronize()
-        extras['index_gather_ms'] = round((time.perf_counter() - t1) * 1e3, 3)
-        extras['gathered_rows'] = int(c_all.shape[0])
-        extras['gathered_kmax'] = int(i_all.shape[1])
+    if args.full:
+        extras['index_gather_ms'] = None
+        if d.dist is not None:
+            gather_onsets(counts, idx)                       # warm-up (communicator set-up)
+            torch.cuda.synchronize()
+            d.barrier()
+            t1 = time.perf_counter()
+            c_all, i_all = gather_onsets(counts, idx)
+            torch.cuda.synchronize()
+            extras['index_gather_ms'] = round((time.perf_counter() - t1) * 1e3, 3)
+            extras['gathered_rows'] = int(c_all.shape[0])
+            extras['gathered_kmax'] = int(i_all.shape[1])
 
     # secondary measurement: the exact-fp32 parity-baseline mode, same workload (outside the timed region)
-    if args.precision != 'fp32' and not args.no_fp32_extra and cfg != 'C4':
+    if args.full and args.precision != 'fp32' and not args.no_fp32_extra and cfg != 'C4':
         m32 = StofNet(upsample_factor=R, precision='fp32')
         m32.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
         m32 = m32.to(dev).eval()
@@ -795,7 +803,7 @@ def infer_bench(args):
         # profiler, tools/profile_bench.sh): the figure is the committed record of such a pass and is labelled as one
         traffic, traffic_source = None, None
         tpath = os.path.join(ROOT, 'profiles', 'traffic_latest.json')
-        if os.path.exists(tpath) and cfg == 'C2' and rows == 4096 and args.precision != 'fp32':
+        if args.full and os.path.exists(tpath) and cfg == 'C2' and rows == 4096 and args.precision != 'fp32':
             try:
                 rec = json.load(open(tpath))
                 traffic = rec.get('body_sweep_hbm_bytes_per_launch')
@@ -821,13 +829,13 @@ def infer_bench(args):
         out['whole_forward_tflops'] = round(total_flops(rows, L, R) * d.world * args.steps / dt / 1e12, 2)
         out['extras'] = extras
         out['ranks'] = census
-        if not args.no_cpu_baseline and d.world == 1:       # rank 0 at N = 1 only (the process group is already closed)
+        if args.full and not args.no_cpu_baseline and d.world == 1:   # rank 0 at N = 1 only (the process group is already closed)
             srows = args.cpu_sample_rows or (256 if cfg != 'C4' else 128)
             srows = min(srows, rows)
             xs = x[:srows].cpu().numpy()
             out['cpu_baseline'] = cpu_baseline(sd, R, L, xs, y[:srows] if cfg != 'C4' else model(x[:srows]),
                                                idx[:srows], threshold=th)
-        if cfg == 'C2' and d.world == 1 and not args.no_extra_configs and not args.rows:
+        if args.full and cfg == 'C2' and d.world == 1 and not args.no_extra_configs and not args.rows:
             # BASELINE.json configs[2..4] under the same clock, after the headline's timed region (headline keys unchanged)
             del y
             torch.cuda.empty_cache()

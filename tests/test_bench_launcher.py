@@ -143,6 +143,25 @@ def test_dump_outputs_of_two_runs_are_identical(tmp_path, config, rows):
             assert np.array_equal(a, b), f
 
 
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_full_adds_the_rest(tmp_path):
+    """A plain run times its steps and prints the line; --full adds, after the same timed steps, the CPU baseline with its
+    parity check, the pickers, the fused onsets and the exact-fp32 mode."""
+    recs = {}
+    for mode in ('plain', 'full'):
+        p = run(['--rows', '64', '--steps', '2', '--warmup', '1', '--cpu-sample-rows', '8'] + (['--full'] if mode == 'full' else []),
+                env={'STOF_BENCH_LOGDIR': str(tmp_path)}, timeout=400)
+        assert p.returncode == 0, p.stderr[-2000:]
+        recs[mode] = json_lines(p.stdout)[-1]
+    plain, full = recs['plain'], recs['full']
+    for k in ('metric', 'unit', 'higher_is_better', 'dtype', 'steps', 'warmup', 'config'):
+        assert plain[k] == full[k], k
+    assert plain['value'] > 0 and plain['ms_per_step'] > 0 and plain['kernels_ms']['body_sweep'] > 0
+    assert 'cpu_baseline' not in plain and set(plain['extras']) == {'auto_mode_fp32_rerun_taken'}
+    assert full['cpu_baseline']['parity_on_sample']['rows'] == 8
+    assert {'picker_argmax_ms', 'fused_argmax_onsets', 'fp32_exact_mode', 'index_gather_ms'} <= set(full['extras'])
+
+
 def test_under_torch_distributed_run_like_the_driver(tmp_path):
     """The driver's N > 1 launch line: torch.distributed.run provides RANK / WORLD_SIZE / MASTER_*."""
     import socket

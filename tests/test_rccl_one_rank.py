@@ -95,10 +95,10 @@ def test_one_rank_nccl_group_takes_every_collective_of_the_path():
 @pytest.mark.gpu
 @pytest.mark.parametrize('config,extra', [('C2', ['--rows', '512']), ('C5', ['--rows', '8'])])
 def test_bench_runs_through_a_one_rank_rccl_group(config, extra):
-    """bench.py --gpus 1 with the process group forced: Dist creates the nccl group, the barriers / MAX timing all-reduce /
+    """bench.py --gpus 1 --full with the process group forced: Dist creates the nccl group, the barriers / MAX timing all-reduce /
     census run on RCCL, C2 gathers its onset indices over it, C5 all-reduces the gradient bucket every step."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--config', config,
-           '--no-cpu-baseline', '--no-fp32-extra', '--no-extra-configs'] + extra
+           '--full', '--no-cpu-baseline', '--no-fp32-extra', '--no-extra-configs'] + extra
     pr = subprocess.run(cmd, env=_env(STOF_FORCE_PROCESS_GROUP='1', STOF_FORCE_COLLECTIVES='1'), cwd=ROOT, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, timeout=400)
     assert pr.returncode == 0, pr.stderr.decode(errors='replace')[-3000:]

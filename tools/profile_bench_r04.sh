@@ -5,10 +5,10 @@ set -euo pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" && export TMPDIR=/tmp
 O=gpurun_out/r04
 T="timeout -k 10 420"
-$T python3 bench.py > ${O}_bench_default.json 2> ${O}_bench_default.err
-$T python3 bench.py --config C5 --train-precision fp32 > ${O}_bench_c5_fp32.json 2> ${O}_bench_c5_fp32.err
-$T python3 bench.py --precision fp32 --no-fp32-extra --no-extra-configs > ${O}_bench_c2_fp32.json 2> ${O}_bench_c2_fp32.err
-$T python3 bench.py --config C5 --trainer autograd > ${O}_bench_c5_f16x3_autograd.json 2> ${O}_bench_c5_f16x3_autograd.err
+$T python3 bench.py --full > ${O}_bench_default.json 2> ${O}_bench_default.err
+$T python3 bench.py --full --config C5 --train-precision fp32 > ${O}_bench_c5_fp32.json 2> ${O}_bench_c5_fp32.err
+$T python3 bench.py --full --precision fp32 --no-fp32-extra --no-extra-configs > ${O}_bench_c2_fp32.json 2> ${O}_bench_c2_fp32.err
+$T python3 bench.py --full --config C5 --trainer autograd > ${O}_bench_c5_f16x3_autograd.json 2> ${O}_bench_c5_f16x3_autograd.err
 echo benches done
 PMC1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS"
 PMC2="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU GRBM_GUI_ACTIVE"
