@@ -36,6 +36,15 @@ from .sample_shuffle import SampleShuffle1D
 _PRECISIONS = {'fp32': _lib.PREC_FP32, 'f16x3': _lib.PREC_F16X3, 'auto': _lib.PREC_F16X3}
 
 
+def raise_sgb_shape_error(L, scale):
+    """The reference's two failures of a SemiGlobalBlock that pools L samples by `scale`, with its messages: an empty
+    max-pool (models/stofnet.py:103), else an odd remainder at the residual add (:115).  Returns if neither."""
+    if L // scale == 0:
+        raise RuntimeError(_lib.status_string(_lib.STOF_ERR_POOL_EMPTY))
+    if (L - L // scale * scale) % 2:
+        raise RuntimeError(f'The size of tensor a ({L}) must match the size of tensor b ({L - 1}) at non-singleton dimension 2')
+
+
 class SemiGlobalBlock(nn.Module):
     """Parameter holder mirroring models/stofnet.py:80-96 (same attribute names)."""
 
@@ -58,7 +67,7 @@ class SemiGlobalBlock(nn.Module):
         channel-last MFMA convolution, pooling and upsample-add kernels the training path uses (exact fp32).  The NCL <->
         channel-last transposes at the boundary are torch copies.  Any C = in_channels = out_channels (the add at :115
         needs them equal), any odd kernel size up to 9, sample_scale 2..256; no autograd graph."""
-        from .training import TrainEngine
+        from .training import LayerKernels
         _lib.require_device(x, 'x')
         cin = self.contract_conv.in_channels
         if x.dim() != 3 or x.shape[1] != cin:
@@ -69,17 +78,15 @@ class SemiGlobalBlock(nn.Module):
                                       'kernel sizes up to 9')
         n, _, L = x.shape
         S = int(self.sample_scale)
-        if L // S == 0:
-            raise RuntimeError(_lib.status_string(_lib.STOF_ERR_POOL_EMPTY))
-        p = L - L // S * S
-        if p % 2:
-            raise RuntimeError(f'The size of tensor a ({L}) must match the size of tensor b ({L - 1}) at non-singleton dimension 2')
-        eng = TrainEngine(x.device, 1, True, 'fp32', scale=S)
+        raise_sgb_shape_error(L, S)
+        if not 2 <= S <= 256:
+            raise NotImplementedError('SemiGlobalBlock sample_scale must be in [2, 256] for the gfx950 kernels')
+        kern = LayerKernels(x.device, _lib.PREC_FP32)
         with torch.cuda.device(x.device):
             a = x.detach().float().permute(0, 2, 1).contiguous()
-            out = eng._sgb_forward(a, eng._repack(self.contract_conv.weight.detach(), False), self.contract_conv.bias.detach(),
-                                   eng._repack(self.expand_conv.weight.detach(), False), self.expand_conv.bias.detach(),
-                                   width=cin, K=K)[0]
+            out = kern._sgb_forward(a, kern._repack(self.contract_conv.weight.detach(), False), self.contract_conv.bias.detach(),
+                                    kern._repack(self.expand_conv.weight.detach(), False), self.expand_conv.bias.detach(),
+                                    S, width=cin, K=K)[0]
             return out.permute(0, 2, 1).contiguous()
 
 
@@ -215,13 +222,8 @@ class StofNet(nn.Module):
                                                _lib.ptr(self._workspace), self._workspace.numel(),
                                                _lib.stream_ptr(x.device), _events,
                                                _lib.ptr(self._status) if self.precision == 'f16x3' else None)
-        if code == _lib.STOF_ERR_ODD_SGB_REMAINDER:
-            # same failure as models/stofnet.py:115
-            got = L // 80 * 80 + 2 * ((L - L // 80 * 80) // 2)
-            raise RuntimeError(f'The size of tensor a ({L}) must match the size of tensor b ({got}) at '
-                               f'non-singleton dimension 2')
-        if code == _lib.STOF_ERR_POOL_EMPTY:
-            raise RuntimeError(_lib.status_string(code))      # the reference's message (models/stofnet.py:103)
+        if code in (_lib.STOF_ERR_ODD_SGB_REMAINDER, _lib.STOF_ERR_POOL_EMPTY):
+            raise_sgb_shape_error(L, int(self.semi_global_scale))
         _lib.check(code, 'stof_forward')
         return y
 
@@ -357,13 +359,11 @@ class StofNet(nn.Module):
         # train_precision='f16x3' behind loss.backward(): a backward since the last check produced a non-finite gradient (that
         # step's gradients were zeroed on the device).  The next backward makes the same check in the host read it needs anyway.
         for eng in self._engines.values():
-            word = getattr(eng, '_bwd_overflow', None)
-            if word is not None:
-                eng._bwd_overflow = None
-                if float(word.item()) != 0.0:
-                    raise FloatingPointError("StofNet(train_precision='f16x3'): a backward produced a non-finite gradient (a "
-                                             "back-propagated value left the fp16 range; its gradients were zeroed); train with "
-                                             "train_precision='fp32'")
+            word = eng.take_bwd_overflow()
+            if word is not None and float(word.item()) != 0.0:
+                raise FloatingPointError("StofNet(train_precision='f16x3'): a backward produced a non-finite gradient (a "
+                                         "back-propagated value left the fp16 range; its gradients were zeroed); train with "
+                                         "train_precision='fp32'")
 
     def _initialize_weights(self):
         """models/stofnet.py:69-77."""

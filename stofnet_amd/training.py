@@ -2,24 +2,26 @@
 main.py:204-248): forward with saved activations, the Gaussian-mask loss, the full backward pass,
 AdamW, and the DDP-style gradient all-reduce (one flat 2.58 MB bucket over RCCL).
 
-Everything numerical runs in `stofnet_amd/csrc/train.hip` through the C ABI, exact fp32, layer by
-layer on channel-last [N][L][C] activations (the backward pass needs every layer's activation, so
-the fused inference sweep does not apply).  PyTorch only owns the device buffers.
+Everything numerical runs in `stofnet_amd/csrc/train.hip` through the C ABI on channel-last [N][L][C]
+activations: exact fp32 layer by layer, or split fp16 (f16x3) with the body of the shipped geometry as one
+fused sweep per direction that also writes every layer's activation.  PyTorch only owns the device buffers.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
+from dataclasses import dataclass
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import _lib
-from .stofnet import StofNet
+from .stofnet import StofNet, raise_sgb_shape_error
 
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
-BODY_CONVS = tuple(f'conv{i}' for i in range(2, 13))
+SG = 'semi_global_block.'
 
 
 def gaussian_kernel(size, sigma=1.0):
@@ -30,63 +32,38 @@ def gaussian_kernel(size, sigma=1.0):
 
 
 class _LazyRepack(dict):
-    """name -> kernel-layout image of a weight, packed on first use: which images a step needs depends on the route its
-    kernels take (the fused SemiGlobalBlock forward packs its own, the sparse backward and conv_last's data-gradient kernel
-    read the raw weights) -- in the default C5 step three of five images were packed and never read.  Keys are known up
-    front (`name in images` decides the backward route)."""
+    """layer name -> kernel-layout image of its weight, packed on first use: which images a step needs depends on the route
+    its kernels take (the fused SemiGlobalBlock forward packs its own, the sparse backward and conv_last's data-gradient
+    kernel read the raw weights) -- in the default C5 step three of five images were packed and never read."""
 
-    def __init__(self, engine, weights, flip):
+    def __init__(self, kernels, params, flip):
         super().__init__()
-        self._engine, self._weights, self._flip = engine, weights, flip
-
-    def __contains__(self, k):
-        return k in self._weights
+        self._kernels, self._params, self._flip = kernels, params, flip
 
     def __missing__(self, k):
-        img = self[k] = self._engine._repack(self._weights[k], self._flip)
+        img = self[k] = self._kernels._repack(self._params[k + '.weight'], self._flip)
         return img
 
 
-class TrainEngine:
-    """Layer-by-layer forward with saved activations and the full backward pass of StofNet on the gfx950 training
-    kernels (`stof_train_*`), on explicit parameter / gradient dictionaries.  Shared by `StofNetTrainer` (fused loss
-    kernels + AdamW kernel on one flat buffer) and by the autograd boundary of `StofNet.forward` in train mode
-    (`StofNetFunction`: torch computes the loss and owns the optimizer, as in the reference's main.py:221-248)."""
+class LayerKernels:
+    """Thin wrappers over the channel-last layer kernels of the C ABI on one device in one MFMA mode, without any network
+    geometry.  `prec` 0 = exact fp32, 1 = split fp16 (f16x3): the arithmetic of every 64/512-channel convolution."""
 
-    def __init__(self, dev, r, sgb, precision='fp32', scale=80, num_blocks=13, body_kernel=7):
-        if precision not in ('fp32', 'f16x3'):
-            raise ValueError("precision must be 'fp32' or 'f16x3'")
-        self.prec = 1 if precision == 'f16x3' else 0       # arithmetic of every 64/512-channel convolution: forward, data gradient, weight gradient
-        self.dev, self.r, self.sgb = dev, int(r), bool(sgb)
-        # models/stofnet.py:11: any num_blocks >= 4 (the reference's forward reads the loop variable of :52 at :60) and any odd
-        # body kernel the layer kernels take; the fused sweeps serve the shipped 13 x k7 geometry, everything else runs
-        # layer by layer on the channel-last MFMA kernels
-        self.nb, self.kb = int(num_blocks), int(body_kernel)
-        if self.nb < 4:
-            raise NotImplementedError('StofNet: num_blocks < 4 fails in the reference (models/stofnet.py:60)')
-        if self.kb not in (1, 3, 5, 7):
-            raise NotImplementedError('StofNet: the gfx950 layer kernels take body kernel sizes 1, 3, 5, 7')
-        # SemiGlobalBlock geometry (models/stofnet.py:83-85): pool / upsample by `scale`, feat_scale = max(1, scale // 10)
-        self.scale = int(scale)
-        self.cmid = 64 * max(1, self.scale // 10)
-        # split-fp16 mode: conv2..conv12 + conv_last of the forward run as ONE fused sweep that also writes every layer's
-        # output for the backward pass (stof_train_sweep) instead of twelve layer launches; STOF_TRAIN_SWEEP=0 keeps the layers
-        import os
-        self.sweep = (self.prec == 1 and (not self.sgb or self.scale == 80) and self.nb == 13 and self.kb == 7
-                      and os.environ.get('STOF_TRAIN_SWEEP', '1') != '0'
-                      and os.environ.get('STOF_BODY16', '1') != '0')
-        self._sweep_blob = None
-        # SemiGlobalBlock backward from the pool's sparse gradient (STOF_TRAIN_SGB_SPARSE=0: dense route, for A/B runs and tests)
-        self.sparse_sgb = os.environ.get('STOF_TRAIN_SGB_SPARSE', '1') != '0'
-        self.sparse_sgb_dgrad = os.environ.get('STOF_TRAIN_SGB_SPARSE_DGRAD', '1') != '0'
-        if self.sgb and not 2 <= self.scale <= 256:
-            raise NotImplementedError('SemiGlobalBlock sample_scale must be in [2, 256] for the gfx950 kernels')
-        self._gscale = 1.0
-        self.g = {}
+    def __init__(self, dev, prec):
+        self.dev, self.prec = dev, int(prec)
+        self._scratch_bufs = {}
 
-    # ---- thin wrappers over the C ABI ---------------------------------------------------------
     def _st(self):
         return _lib.stream_ptr(self.dev)
+
+    def _scratch(self, name, nbytes):
+        """The uint8 device buffer `name`, grown on demand to at least `nbytes`."""
+        # (workspaces and packed-weight blobs that live from step to step: a graphed step allocates them in its eager warm-up
+        # passes, never inside the capture)
+        buf = self._scratch_bufs.get(name)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._scratch_bufs[name] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.dev)
+        return buf
 
     def _conv(self, x, w_tm, bias, cin, cout, K, act=ACT_NONE, residual=None, saved=None):
         n, L = x.shape[0], x.shape[1]
@@ -104,120 +81,195 @@ class TrainEngine:
                    'stof_train_repack')
         return out
 
-    def _wgrad(self, x, dy, name, cin, cout, K):
+    def _wgrad(self, x, dy, dw, db, cin, cout, K, out_scale=1.0):
+        """dw [cout, cin, K], db [cout] = out_scale * weight / bias gradient of the convolution with input x, output gradient dy."""
         n, L = x.shape[0], x.shape[1]
-        need = _lib.lib().stof_train_wgrad_workspace_bytes(cin, cout, K)
-        ws = getattr(self, '_wgrad_ws', None)
-        if ws is None or ws.numel() < need:
-            ws = self._wgrad_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-        _lib.check(_lib.lib().stof_train_wgrad(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(self.g[name + '.weight']),
-                                               _lib.ptr(self.g[name + '.bias']), n, L, cin, cout, K, 1.0 / self._gscale, self.prec, _lib.ptr(ws),
-                                               ws.numel(),
-                                               self._st()), 'stof_train_wgrad')
+        ws = self._scratch('_wgrad_ws', _lib.lib().stof_train_wgrad_workspace_bytes(cin, cout, K))
+        _lib.check(_lib.lib().stof_train_wgrad(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), _lib.ptr(db), n, L, cin, cout, K,
+                                               out_scale, self.prec, _lib.ptr(ws), ws.numel(), self._st()), 'stof_train_wgrad')
 
     def _add(self, a, b):
         out = torch.empty_like(a)
         _lib.check(_lib.lib().stof_train_add(_lib.ptr(a), _lib.ptr(b), _lib.ptr(out), a.numel(), self._st()), 'stof_train_add')
         return out
 
-    # ---- forward (activations kept) and backward, on explicit parameter / gradient dictionaries --------------
+    def _sgb_head(self, a1, w_contract, b_contract, w_expand, b_expand, scale, width=64, K=5):
+        """contract conv -> lrelu -> max-pool by `scale` -> expand conv -> lrelu (models/stofnet.py:100-107) on channel-last a1
+        [N, L, width]; inside StofNet width = 64 and K = 5, the standalone block (models/stofnet.py:80) takes any."""
+        lib, st = _lib.lib(), self._st()
+        n, L = a1.shape[0], a1.shape[1]
+        cm = width * max(1, scale // 10)
+        P = L // scale
+        c = self._conv(a1, w_contract, b_contract, width, cm, K, ACT_LRELU)
+        pooled = torch.empty((n, max(P, 1), cm), dtype=torch.float32, device=self.dev)[:, :P]
+        arg = torch.empty((n, max(P, 1), cm), dtype=torch.uint8, device=self.dev)[:, :P]
+        _lib.check(lib.stof_train_pool(_lib.ptr(c), _lib.ptr(pooled), _lib.ptr(arg), n, L, P, cm, scale, st), 'stof_train_pool')
+        e = self._conv(pooled, w_expand, b_expand, cm, width, K, ACT_LRELU)
+        return c, pooled, arg, e
+
+    def _sgb_forward(self, a1, w_contract, b_contract, w_expand, b_expand, scale, width=64, K=5):
+        """SemiGlobalBlock.forward (models/stofnet.py:98-117) on channel-last a1 [N, L, width]:
+        a1 + pad(upsample(lrelu(expand(maxpool(lrelu(contract(a1))))))).  Returns (out, c, pooled, arg, e)."""
+        lib, st = _lib.lib(), self._st()
+        n, L = a1.shape[0], a1.shape[1]
+        P = L // scale
+        rem = L - scale * P
+        c, pooled, arg, e = self._sgb_head(a1, w_contract, b_contract, w_expand, b_expand, scale, width, K)
+        out = torch.empty_like(a1)
+        if width == 64:
+            _lib.check(lib.stof_train_upsample_add(_lib.ptr(a1), _lib.ptr(e), _lib.ptr(out), n, L, P, rem // 2, scale, st),
+                       'stof_train_upsample_add')
+        else:
+            _lib.check(lib.stof_train_upsample_add_c(_lib.ptr(a1), _lib.ptr(e), _lib.ptr(out), n, L, P, rem // 2, scale, width, st),
+                       'stof_train_upsample_add_c')
+        return out, c, pooled, arg, e
+
+
+@dataclass
+class SavedForward:
+    """What one forward keeps for its backward.  `sweep` / `split` are the route of the step, decided once in the forward:
+    the body ran as the fused sweep, and that sweep wrote its dumps as split rows.  Fields a route does not use are None."""
+    p: dict                     # name -> parameter tensor of this step
+    bwd: _LazyRepack            # layer name -> flipped (data-gradient) weight image
+    x: torch.Tensor             # [N, L] input frame
+    a1: torch.Tensor            # [N, L, 64] relu(conv1)
+    P: int                      # pooled length of the SemiGlobalBlock (0 without one)
+    sweep: bool
+    split: bool = False
+    c: torch.Tensor = None      # SemiGlobalBlock: contract conv output (layer route only), pooled map, arg-max, expand conv output
+    pooled: torch.Tensor = None
+    arg: torch.Tensor = None
+    e: torch.Tensor = None
+    v: dict = None              # layer route: i -> output of conv{i} (v[1] = the body's input x0)
+    x6: torch.Tensor = None     # output of the second-last conv = conv_last's input
+    desc: _lib.NetDesc = None   # sweep route: the sweeps' descriptor, the forward dump and its tensors
+    dump: torch.Tensor = None
+    xs: list = None             # xs[k] = residual state x_k (k = 0..5), ys[k] = lrelu(conv{2k+2}(x_k))
+    ys: list = None
+
+
+class TrainEngine(LayerKernels):
+    """Forward with saved activations and the full backward pass of StofNet on the gfx950 training kernels
+    (`stof_train_*`), on explicit parameter / gradient dictionaries.  Shared by `StofNetTrainer` (fused loss
+    kernels + AdamW kernel on one flat buffer) and by the autograd boundary of `StofNet.forward` in train mode
+    (`StofNetFunction`: torch computes the loss and owns the optimizer, as in the reference's main.py:221-248)."""
+    # Two routes, fixed per engine by `self.sweep`: the fused sweeps (body forward and backward as one launch each plus one
+    # batched weight-gradient launch) or layer by layer.  Within the sweep route the forward sweep decides whether the dumps
+    # are split rows (`SavedForward.split`) and the backward follows it.
+
+    def __init__(self, dev, r, sgb, precision='fp32', scale=80, num_blocks=13, body_kernel=7):
+        if precision not in ('fp32', 'f16x3'):
+            raise ValueError("precision must be 'fp32' or 'f16x3'")
+        super().__init__(dev, 1 if precision == 'f16x3' else 0)
+        self.r, self.sgb = int(r), bool(sgb)
+        # models/stofnet.py:11: any num_blocks >= 4 (the reference's forward reads the loop variable of :52 at :60) and any odd
+        # body kernel the layer kernels take; the fused sweeps serve the shipped 13 x k7 geometry, everything else runs
+        # layer by layer on the channel-last MFMA kernels
+        self.nb, self.kb = int(num_blocks), int(body_kernel)
+        if self.nb < 4:
+            raise NotImplementedError('StofNet: num_blocks < 4 fails in the reference (models/stofnet.py:60)')
+        if self.kb not in (1, 3, 5, 7):
+            raise NotImplementedError('StofNet: the gfx950 layer kernels take body kernel sizes 1, 3, 5, 7')
+        # SemiGlobalBlock geometry (models/stofnet.py:83-85): pool / upsample by `scale`, feat_scale = max(1, scale // 10)
+        self.scale = int(scale)
+        self.cmid = 64 * max(1, self.scale // 10)
+        if self.sgb and not 2 <= self.scale <= 256:
+            raise NotImplementedError('SemiGlobalBlock sample_scale must be in [2, 256] for the gfx950 kernels')
+        # split-fp16 mode, shipped geometry: conv2..conv12 + conv_last of the forward run as ONE fused sweep that also writes
+        # every layer's output for the backward pass (stof_train_sweep) instead of twelve layer launches, and the backward as
+        # one sweep + one batched weight-gradient launch.  STOF_BODY16=0 changes the packed fragment order the sweeps read.
+        self.sweep = (self.prec == 1 and (not self.sgb or self.scale == 80) and self.nb == 13 and self.kb == 7
+                      and os.environ.get('STOF_BODY16', '1') != '0')
+        self.sgb_sparse_taken = False       # bench.py: whether the last backward ran the sparse SemiGlobalBlock kernels
+        self._bwd_overflow = None           # StofNetFunction: range-guard word of the last f16x3 backward, not yet read
+
+    def take_bwd_overflow(self):
+        """The pending range-guard word (1-element device tensor, non-zero = gradients were non-finite) or None; clears it."""
+        word, self._bwd_overflow = self._bwd_overflow, None
+        return word
+
+    # ---- forward (activations kept) --------------------------------------------------------------------------
     def _forward_saved(self, p, frame, keep=True):
-        """models/stofnet.py:42-67 layer by layer, every activation kept for the backward pass.
-        Returns (pred [N, L*r] = conv_last's channel-last output = the sample-shuffled prediction, saved)."""
-        lib = _lib.lib()
+        """models/stofnet.py:42-67, every activation kept for the backward pass (keep=False: inference, nothing kept).
+        Returns (pred [N, L*r] = conv_last's channel-last output = the sample-shuffled prediction, SavedForward or None)."""
         _lib.require_device(frame, 'frame')
-        r = self.r
         x = frame.detach().reshape(frame.shape[0], frame.shape[-1]).contiguous().float()
         n, L = x.shape
-        S, cm = self.scale, self.cmid
-        P = L // S if self.sgb else 0
-        rem = L - S * P
-        if self.sgb and P == 0:
-            raise RuntimeError(_lib.status_string(_lib.STOF_ERR_POOL_EMPTY))     # the reference's max_pool1d error
-        if self.sgb and rem % 2:
-            raise RuntimeError(f'The size of tensor a ({L}) must match the size of tensor b ({L - 1}) at non-singleton dimension 2')
-        sg = 'semi_global_block.'
-        st = self._st()
-        use_sweep = self.sweep and 'conv2.weight' in p
-        head = ('semi_global_block.',) if use_sweep else ('conv', 'semi_global_block.')        # layers that still run one by one
-        fwd = _LazyRepack(self, {k[:-7]: w for k, w in p.items()
-                                 if k.endswith('.weight') and k != 'conv1.weight' and k.startswith(head)}, False)
-        sweep_bwd = use_sweep and os.environ.get('STOF_TRAIN_SWEEP_BWD', '1') != '0'       # conv2..conv12 data gradients: one sweep too
-        bwd = _LazyRepack(self, {k[:-7]: w for k, w in p.items() if k.endswith('.weight') and k != 'conv1.weight'
-                                 and not (sweep_bwd and k[:-7] in BODY_CONVS)}, True) if keep else None
-        a1 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_train_conv1(_lib.ptr(x), _lib.ptr(p['conv1.weight']), _lib.ptr(p['conv1.bias']), _lib.ptr(a1),
-                                        n, L, st), 'stof_train_conv1')
-        c = pooled = arg = e = None
-        if use_sweep:
-            # SemiGlobalBlock up to the expand conv on the layer kernels (the backward pass needs c / pooled / arg); its
-            # up-sampled map is added inside the sweep, which recomputes relu(conv1) from x
-            if self.sgb and os.environ.get('STOF_TRAIN_SGB_FUSED', '1') != '0':
-                # contract conv + lrelu + max-pool fused as in inference (no [N, L, 512] tensor), with the pool's arg-max
-                pooled = torch.empty((n, P, cm), dtype=torch.float32, device=self.dev)
-                arg = torch.empty((n, P, cm), dtype=torch.uint8, device=self.dev)
-                if getattr(self, '_sgb_blob', None) is None:
-                    self._sgb_blob = torch.empty(lib.stof_train_sgb_blob_bytes(), dtype=torch.uint8, device=self.dev)
-                _lib.check(lib.stof_train_sgb_contract_pool(_lib.ptr(p['conv1.weight'].contiguous()), _lib.ptr(p['conv1.bias'].contiguous()),
-                                                            _lib.ptr(p[sg + 'contract_conv.weight'].contiguous()),
-                                                            _lib.ptr(p[sg + 'contract_conv.bias'].contiguous()), _lib.ptr(self._sgb_blob),
-                                                            _lib.ptr(x), _lib.ptr(pooled), _lib.ptr(arg), n, L, st),
-                           'stof_train_sgb_contract_pool')
-                e = self._conv(pooled, fwd[sg + 'expand_conv'], p[sg + 'expand_conv.bias'], cm, 64, 5, ACT_LRELU)
-            elif self.sgb:
-                c, pooled, arg, e = self._sgb_head(a1, fwd[sg + 'contract_conv'], p[sg + 'contract_conv.bias'],
-                                                   fwd[sg + 'expand_conv'], p[sg + 'expand_conv.bias'])
-            desc = _lib.NetDesc(int(r), 80 if self.sgb else 1, _lib.PREC_F16X3, 0)
-            import ctypes
-            nbytes = lib.stof_train_sweep_blob_bytes(ctypes.byref(desc))
-            if self._sweep_blob is None or self._sweep_blob.numel() < nbytes:
-                self._sweep_blob = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-            names = ['conv1'] + [f'conv{i}' for i in range(2, 13)] + ['conv_last']
-            arr = (ctypes.c_void_p * 26)()
-            for i, nm in enumerate(names):
-                arr[2 * i] = _lib.ptr(p[nm + '.weight'].contiguous())
-                arr[2 * i + 1] = _lib.ptr(p[nm + '.bias'].contiguous())
-            _lib.check(lib.stof_train_sweep_pack(ctypes.byref(desc), arr, _lib.ptr(self._sweep_blob), st), 'stof_train_sweep_pack')
-            dump = torch.empty(lib.stof_train_sweep_dump_floats(n, L), dtype=torch.float32, device=self.dev)
-            z = torch.empty((n, L * r), dtype=torch.float32, device=self.dev)
-            # r4: when the backward pass runs as one sweep + one batched weight-gradient launch, the dumps are SPLIT ROWS
-            # ([64 x fp16 hi | 64 x fp16 lo] per 256-byte row: the halves the sweeps compute anyway) and the weight-gradient
-            # kernel stages them without converting.  STOF_TRAIN_SPLIT_DUMPS=0: fp32 dumps everywhere (A/B runs).
-            split = (keep and sweep_bwd and self.prec == 1 and os.environ.get('STOF_TRAIN_WGRAD_BATCH', '1') != '0'
-                     and os.environ.get('STOF_TRAIN_SPLIT_DUMPS', '1') != '0')
-            if split:
-                code = lib.stof_train_sweep_split(ctypes.byref(desc), _lib.ptr(self._sweep_blob), _lib.ptr(x), _lib.ptr(e), _lib.ptr(dump),
-                                                  _lib.ptr(z), n, L, st)
-                if code == _lib.STOF_ERR_UNSUPPORTED:
-                    split = False
-                else:
-                    _lib.check(code, 'stof_train_sweep_split')
-            if not split:
-                _lib.check(lib.stof_train_sweep(ctypes.byref(desc), _lib.ptr(self._sweep_blob), _lib.ptr(x), _lib.ptr(e), _lib.ptr(dump),
-                                                _lib.ptr(z), n, L, st), 'stof_train_sweep')
-            if not keep:
-                return z, None
-            t = dump[:12 * n * L * 64].view(12, n, L, 64)
-            xs = [t[0]] + [t[2 + 2 * k] for k in range(5)]
-            ys = [t[1 + 2 * k] for k in range(5)]
-            v = {1: xs[0]}
-            for k in range(5):
-                v[2 * k + 2], v[2 * k + 3] = ys[k], xs[k + 1]
-            saved = dict(x=x, a1=a1, c=c, pooled=pooled, arg=arg, e=e, xs=xs, ys=ys, v=v, x6=t[11], bwd=bwd, n=n, L=L, P=P, rem=rem,
-                         _dump=dump, split=split, desc=desc, wdev=[p[f'conv{i}.weight'] for i in range(2, 13)],
-                         wc=p.get(sg + 'contract_conv.weight'), wl=p['conv_last.weight'], w1=p['conv1.weight'])
-            return z, saved
+        P = L // self.scale if self.sgb else 0
         if self.sgb:
-            x0, c, pooled, arg, e = self._sgb_forward(a1, fwd[sg + 'contract_conv'], p[sg + 'contract_conv.bias'],
-                                                      fwd[sg + 'expand_conv'], p[sg + 'expand_conv.bias'])
-        else:
-            x0 = a1
-        if not keep:
-            del c, pooled, arg, e
-            c = pooled = arg = e = None
+            raise_sgb_shape_error(L, self.scale)
+        a1 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
+        _lib.check(_lib.lib().stof_train_conv1(_lib.ptr(x), _lib.ptr(p['conv1.weight']), _lib.ptr(p['conv1.bias']), _lib.ptr(a1),
+                                               n, L, self._st()), 'stof_train_conv1')
+        s = SavedForward(p=p, bwd=_LazyRepack(self, p, True) if keep else None, x=x, a1=a1, P=P, sweep=self.sweep)
+        z = (self._forward_sweep if self.sweep else self._forward_layers)(s, keep)
+        return z, (s if keep else None)
+
+    def _sgb_contract_pool(self, s):
+        """Sweep route: contract conv + lrelu + max-pool fused as in inference (no [N, L, 512] tensor), with the pool's arg-max."""
+        lib, p = _lib.lib(), s.p
+        n, L = s.x.shape
+        s.pooled = torch.empty((n, s.P, self.cmid), dtype=torch.float32, device=self.dev)
+        s.arg = torch.empty((n, s.P, self.cmid), dtype=torch.uint8, device=self.dev)
+        blob = self._scratch('_sgb_blob', lib.stof_train_sgb_blob_bytes())
+        _lib.check(lib.stof_train_sgb_contract_pool(_lib.ptr(p['conv1.weight'].contiguous()), _lib.ptr(p['conv1.bias'].contiguous()),
+                                                    _lib.ptr(p[SG + 'contract_conv.weight'].contiguous()),
+                                                    _lib.ptr(p[SG + 'contract_conv.bias'].contiguous()), _lib.ptr(blob),
+                                                    _lib.ptr(s.x), _lib.ptr(s.pooled), _lib.ptr(s.arg), n, L, self._st()),
+                   'stof_train_sgb_contract_pool')
+
+    def _forward_sweep(self, s, keep):
+        """conv2..conv12 + conv_last as one fused sweep that dumps every layer's output."""
+        lib, st, p, r = _lib.lib(), self._st(), s.p, self.r
+        n, L = s.x.shape
+        # SemiGlobalBlock up to the expand conv in front of the sweep (the backward pass needs pooled / arg / e); its
+        # up-sampled map is added inside the sweep, which recomputes relu(conv1) from x
+        if self.sgb:
+            self._sgb_contract_pool(s)
+            s.e = self._conv(s.pooled, self._repack(p[SG + 'expand_conv.weight'], False), p[SG + 'expand_conv.bias'],
+                             self.cmid, 64, 5, ACT_LRELU)
+        s.desc = desc = _lib.NetDesc(int(r), 80 if self.sgb else 1, _lib.PREC_F16X3, 0)
+        blob = self._scratch('_sweep_blob', lib.stof_train_sweep_blob_bytes(ctypes.byref(desc)))
+        arr = (ctypes.c_void_p * 26)()
+        for i, nm in enumerate(['conv1'] + [f'conv{i}' for i in range(2, 13)] + ['conv_last']):
+            arr[2 * i] = _lib.ptr(p[nm + '.weight'].contiguous())
+            arr[2 * i + 1] = _lib.ptr(p[nm + '.bias'].contiguous())
+        _lib.check(lib.stof_train_sweep_pack(ctypes.byref(desc), arr, _lib.ptr(blob), st), 'stof_train_sweep_pack')
+        s.dump = dump = torch.empty(lib.stof_train_sweep_dump_floats(n, L), dtype=torch.float32, device=self.dev)
+        z = torch.empty((n, L * r), dtype=torch.float32, device=self.dev)
+        # Dumps a backward will read are SPLIT ROWS ([64 x fp16 hi | 64 x fp16 lo] per 256-byte row: the halves the sweeps
+        # compute anyway; the batched weight-gradient kernel stages them without converting) wherever stof_train_sweep_split
+        # takes the shape; fp32 dumps otherwise, and everywhere under STOF_TRAIN_SPLIT_DUMPS=0 (route comparisons).
+        s.split = keep and os.environ.get('STOF_TRAIN_SPLIT_DUMPS', '1') != '0'
+        sweep_args = (ctypes.byref(desc), _lib.ptr(blob), _lib.ptr(s.x), _lib.ptr(s.e), _lib.ptr(dump), _lib.ptr(z), n, L, st)
+        if s.split:
+            code = lib.stof_train_sweep_split(*sweep_args)
+            if code == _lib.STOF_ERR_UNSUPPORTED:
+                s.split = False
+            else:
+                _lib.check(code, 'stof_train_sweep_split')
+        if not s.split:
+            _lib.check(lib.stof_train_sweep(*sweep_args), 'stof_train_sweep')
+        t = dump[:12 * n * L * 64].view(12, n, L, 64)
+        s.xs = [t[0]] + [t[2 + 2 * k] for k in range(5)]
+        s.ys = [t[1 + 2 * k] for k in range(5)]
+        s.x6 = t[11]
+        return z
+
+    def _forward_layers(self, s, keep):
+        """models/stofnet.py:46-64 layer by layer for any num_blocks and body kernel; keep=False drops every activation as
+        soon as nothing ahead reads it."""
+        p, nb, kb, r = s.p, self.nb, self.kb, self.r
+        fwd = _LazyRepack(self, p, False)
+        x0 = s.a1
+        if self.sgb:
+            x0, *kept = self._sgb_forward(s.a1, fwd[SG + 'contract_conv'], p[SG + 'contract_conv.bias'],
+                                          fwd[SG + 'expand_conv'], p[SG + 'expand_conv.bias'], self.scale)
+            if keep:
+                s.c, s.pooled, s.arg, s.e = kept
+            del kept
         # models/stofnet.py:51-62 for any num_blocks: even layers leaky ReLU, odd layers (>= 3) add the running residual
         # and become it; the second-last layer adds res1 = x0.  v[i] = output of conv{i} (v[1] = x0).
-        nb, kb = self.nb, self.kb
         v = {1: x0}
         for i in range(2, nb - 1):
             nm = f'conv{i}'
@@ -232,203 +284,155 @@ class TrainEngine:
         nm = f'conv{nb - 1}'
         x6 = self._conv(v[nb - 2], fwd[nm], p[nm + '.bias'], 64, 64, kb, ACT_NONE, residual=x0)
         z = self._conv(x6, fwd['conv_last'], p['conv_last.bias'], 64, r, 3, ACT_NONE)      # [N, L, r] == shuffled [N, L*r]
-        if not keep:
-            return z.view(n, L * r), None
-        saved = dict(x=x, a1=a1, c=c, pooled=pooled, arg=arg, e=e, v=v, x6=x6, bwd=bwd, n=n, L=L, P=P, rem=rem,
-                     wc=p.get('semi_global_block.contract_conv.weight'), wl=p['conv_last.weight'], w1=p['conv1.weight'])
-        return z.view(n, L * r), saved
+        if keep:
+            s.v, s.x6 = v, x6
+        return z.view(x0.shape[0], x0.shape[1] * r)
 
-    def _sgb_head(self, a1, w_contract, b_contract, w_expand, b_expand, width=64, K=5):
-        """contract conv -> lrelu -> max-pool -> expand conv -> lrelu (models/stofnet.py:100-107) on channel-last a1
-        [N, L, width]; inside StofNet width = 64 and K = 5, the standalone block (models/stofnet.py:80) takes any."""
-        lib, st = _lib.lib(), self._st()
-        n, L = a1.shape[0], a1.shape[1]
-        S = self.scale
-        cm = self.cmid if width == 64 else width * max(1, S // 10)
-        P = L // S
-        c = self._conv(a1, w_contract, b_contract, width, cm, K, ACT_LRELU)
-        pooled = torch.empty((n, max(P, 1), cm), dtype=torch.float32, device=self.dev)[:, :P]
-        arg = torch.empty((n, max(P, 1), cm), dtype=torch.uint8, device=self.dev)[:, :P]
-        _lib.check(lib.stof_train_pool(_lib.ptr(c), _lib.ptr(pooled), _lib.ptr(arg), n, L, P, cm, S, st), 'stof_train_pool')
-        e = self._conv(pooled, w_expand, b_expand, cm, width, K, ACT_LRELU)
-        return c, pooled, arg, e
-
-    def _sgb_forward(self, a1, w_contract, b_contract, w_expand, b_expand, width=64, K=5):
-        """SemiGlobalBlock.forward (models/stofnet.py:98-117) on channel-last a1 [N, L, 64]:
-        a1 + pad(upsample(lrelu(expand(maxpool(lrelu(contract(a1))))))).  Returns (out, c, pooled, arg, e)."""
-        lib, st = _lib.lib(), self._st()
-        n, L = a1.shape[0], a1.shape[1]
-        S = self.scale
-        P = L // S
-        rem = L - S * P
-        c, pooled, arg, e = self._sgb_head(a1, w_contract, b_contract, w_expand, b_expand, width, K)
-        out = torch.empty_like(a1)
-        if width == 64:
-            _lib.check(lib.stof_train_upsample_add(_lib.ptr(a1), _lib.ptr(e), _lib.ptr(out), n, L, P, rem // 2, S, st),
-                       'stof_train_upsample_add')
-        else:
-            _lib.check(lib.stof_train_upsample_add_c(_lib.ptr(a1), _lib.ptr(e), _lib.ptr(out), n, L, P, rem // 2, S, width, st),
-                       'stof_train_upsample_add_c')
-        return out, c, pooled, arg, e
-
+    # ---- backward ----------------------------------------------------------------------------------------------
     def _backward_saved(self, saved, dpred, g, gscale, dx=None):
         """Backward pass from dpred [N, L*r] = gscale * dloss/dpred (gscale a power of two: the f16x3 data-gradient
         convolutions would otherwise work on fp16 subnormals; the weight-gradient kernels multiply by 1/gscale, exact).
         Writes every parameter gradient into the tensors of `g` (name -> tensor of the parameter's shape) and, if `dx`
-        [N, L] is given, the gradient with respect to the input frame into it."""
-        lib = _lib.lib()
-        r, st = self.r, self._st()
-        sg = 'semi_global_block.'
-        n, L, P, rem = saved['n'], saved['L'], saved['P'], saved['rem']
-        xs, ys, v, x6, bwd, a1 = saved.get('xs'), saved.get('ys'), saved['v'], saved['x6'], saved['bwd'], saved['a1']
-        nb, kb = self.nb, self.kb
-        second_last = f'conv{nb - 1}'
-        self._gscale = float(gscale)
-        self.g = g
+        [N, L] is given, the gradient with respect to the input frame into it.  Reads its route off `saved`."""
+        lib, st, r, split = _lib.lib(), self._st(), self.r, saved.split
+        n, L = saved.x.shape
+        inv = 1.0 / float(gscale)
         dz = dpred.view(n, L, r)
-        self._wgrad(x6, dz, 'conv_last', 64, r, 3)
-        # conv_last's data gradient: r input channels would be padded to a 64-channel block by the layer kernels
+        self._wgrad(saved.x6, dz, g['conv_last.weight'], g['conv_last.bias'], 64, r, 3, inv)
+        # conv_last's data gradient: r input channels would be padded to a 64-channel block by the layer kernels.  Split route:
+        # g6 is a split-row tensor as well (the backward sweep's input, conv12's output gradient for the weight-gradient launch
+        # and the long-skip join all take it as such)
         g6 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
-        split = bool(saved.get('split'))          # the forward dumps are split rows: only the sweep + batched route reads them
-        # split route: g6 is a split-row tensor as well (the backward sweep's input, conv12's output gradient for the weight-gradient
-        # launch and the long-skip join all take it as such)
         code = (lib.stof_train_conv_last_dgrad_split if split else lib.stof_train_conv_last_dgrad)(
-            _lib.ptr(dz.contiguous()), _lib.ptr(saved['wl'].contiguous()), _lib.ptr(g6), n, L, r, st)
+            _lib.ptr(dz.contiguous()), _lib.ptr(saved.p['conv_last.weight'].contiguous()), _lib.ptr(g6), n, L, r, st)
         if code == _lib.STOF_ERR_UNSUPPORTED:
-            g6 = self._conv(dz, bwd['conv_last'], None, r, 64, 3)
+            g6 = self._conv(dz, saved.bwd['conv_last'], None, r, 64, 3)
             if split:
                 g6f, g6 = g6, torch.empty_like(g6)
                 _lib.check(lib.stof_train_to_split_rows(_lib.ptr(g6f), _lib.ptr(g6), n * L, st), 'stof_train_to_split_rows')
         else:
             _lib.check(code, 'stof_train_conv_last_dgrad')
-        batch_wgrad = (self.prec == 1 and saved.get('_dump') is not None and second_last not in bwd
-                       and (split or os.environ.get('STOF_TRAIN_WGRAD_BATCH', '1') != '0'))
-        if split and not batch_wgrad:
-            raise RuntimeError('split-row dumps without the backward sweep')
-        if not batch_wgrad:
-            self._wgrad(v[nb - 2], g6, second_last, 64, 64, kb)
-        if saved.get('_dump') is not None and second_last not in bwd:
-            # the eleven data-gradient convolutions conv12^T .. conv2^T as ONE backward sweep (stof_train_sweep_bwd), then the
-            # weight gradients from its dumps: tensor j odd = dL/dx_k, k = (11 - j) / 2; j even = dL/d(pre-activation of conv(12 - j))
-            import ctypes
-            nbytes = lib.stof_train_sweep_blob_bytes(ctypes.byref(saved['desc']))
-            if getattr(self, '_sweep_blob_bwd', None) is None or self._sweep_blob_bwd.numel() < nbytes:
-                self._sweep_blob_bwd = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-            arr = (ctypes.c_void_p * 11)(*[_lib.ptr(w.contiguous()) for w in saved['wdev']])
-            _lib.check(lib.stof_train_sweep_bwd_pack(arr, _lib.ptr(self._sweep_blob_bwd), st), 'stof_train_sweep_bwd_pack')
-            dumpb = torch.empty(lib.stof_train_sweep_dump_floats(n, L), dtype=torch.float32, device=self.dev)
-            _lib.check((lib.stof_train_sweep_bwd_split if split else lib.stof_train_sweep_bwd)(
-                ctypes.byref(saved['desc']), _lib.ptr(self._sweep_blob_bwd), _lib.ptr(g6), _lib.ptr(saved['_dump']),
-                _lib.ptr(dumpb), n, L, st), 'stof_train_sweep_bwd')
-            T = dumpb[:12 * n * L * 64].view(12, n, L, 64)
-            pairs = [(xs[5], g6, 'conv12')] if batch_wgrad else []                      # (input activation, output gradient, layer)
-            for k in range(4, -1, -1):
-                pairs.append((ys[k], T[9 - 2 * k], f'conv{2 * k + 3}'))                 # g_{k+1} = T[11 - 2 (k + 1)]
-                pairs.append((xs[k], T[10 - 2 * k], f'conv{2 * k + 2}'))                # u_k
-            if batch_wgrad:
-                # r4: the eleven k7 weight gradients in ONE launch pair (stof_train_wgrad_batch) instead of eleven launches +
-                # eleven reductions of 58 MB of partials each
-                import ctypes
-                cnt = len(pairs)
-                need = lib.stof_train_wgrad_batch_workspace_bytes(cnt, 7)
-                ws = getattr(self, '_wgrad_batch_ws', None)
-                if ws is None or ws.numel() < need:
-                    ws = self._wgrad_batch_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-                arr = lambda ts: (ctypes.c_void_p * cnt)(*[_lib.ptr(t) for t in ts])
-                if split:
-                    # every x operand is a forward dump tensor (0..10), every dy a backward dump tensor or g6: all split rows
-                    all_bits = (1 << cnt) - 1
-                    _lib.check(lib.stof_train_wgrad_batch_split(arr([a for a, _, _ in pairs]), arr([d for _, d, _ in pairs]),
-                                                                arr([self.g[nm + '.weight'] for _, _, nm in pairs]),
-                                                                arr([self.g[nm + '.bias'] for _, _, nm in pairs]), cnt, all_bits,
-                                                                all_bits, n, L, 7, 1.0 / self._gscale, _lib.ptr(ws), ws.numel(), st),
-                               'stof_train_wgrad_batch_split')
-                else:
-                    _lib.check(lib.stof_train_wgrad_batch(arr([a for a, _, _ in pairs]), arr([d for _, d, _ in pairs]),
-                                                          arr([self.g[nm + '.weight'] for _, _, nm in pairs]),
-                                                          arr([self.g[nm + '.bias'] for _, _, nm in pairs]), cnt, n, L, 7,
-                                                          1.0 / self._gscale, _lib.ptr(ws), ws.numel(), st), 'stof_train_wgrad_batch')
-            else:
-                for a, d, nm in pairs:
-                    self._wgrad(a, d, nm, 64, 64, 7)
-            gg = T[11]                                                                   # dL/dx_0 without the long skip
-        else:
-            # any num_blocks, layer by layer.  Walking down from the second-last layer: an odd layer i holds the TOTAL gradient
-            # gg of its output (its own consumer + the residual add two layers on); its transposed convolution, masked with
-            # lrelu'(v[i-1]), is u = the gradient before the activation of the even layer i-1; that layer's transposed
-            # convolution plus gg (the residual path) is the total gradient of v[i-2].
-            m = nb - 2                                                                # last layer of the loop (:52)
-            if m % 2:
-                gg, u = self._conv(g6, bwd[second_last], None, 64, 64, kb), None        # d/dv[m], v[m] a residual state
-            else:
-                gg, u = None, self._conv(g6, bwd[second_last], None, 64, 64, kb, ACT_LRELU, saved=v[m])
-            for i in range(m, 1, -1):
-                nm = f'conv{i}'
-                if i % 2:
-                    self._wgrad(v[i - 1], gg, nm, 64, 64, kb)
-                    u = self._conv(gg, bwd[nm], None, 64, 64, kb, ACT_LRELU, saved=v[i - 1])
-                else:
-                    self._wgrad(v[i - 1], u, nm, 64, 64, kb)
-                    gg = self._conv(u, bwd[nm], None, 64, 64, kb, residual=gg)      # (gg None for the loop's last layer)
+        gg = (self._backward_body_sweep if saved.sweep else self._backward_body_layers)(saved, g6, g, inv)
         if split:                                                                 # long skip res1 (models/stofnet.py:62)
             g_x0 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
             _lib.check(lib.stof_train_add_split2(_lib.ptr(gg), _lib.ptr(g6), _lib.ptr(g_x0), n * L, st), 'stof_train_add_split2')
         else:
             g_x0 = self._add(gg, g6)
-        if self.sgb and P:
-            e, pooled, arg, c = saved['e'], saved['pooled'], saved['arg'], saved['c']
-            ge = torch.empty((n, P, 64), dtype=torch.float32, device=self.dev)
-            S, cm = self.scale, self.cmid
-            _lib.check(lib.stof_train_upsample_bwd(_lib.ptr(g_x0), _lib.ptr(e), _lib.ptr(ge), n, L, P, rem // 2, S, st),
-                       'stof_train_upsample_bwd')
-            self._wgrad(pooled, ge, sg + 'expand_conv', cm, 64, 5)
-            gpool = self._conv(ge, bwd[sg + 'expand_conv'], None, 64, cm, 5)
-            # The gradient behind the max-pool is zero except at ONE row per (waveform, window, channel).  Where the kernels
-            # take the shape, contract_conv's weight gradient and data gradient come straight from those non-zeros
-            # (stof_train_sgb_contract_wgrad / _dgrad); otherwise -- and with STOF_TRAIN_SGB_SPARSE=0 -- the dense [N, L, cm]
-            # gradient is built (stof_train_pool_bwd) and goes through the layer kernels like every other convolution.
-            U = _lib.STOF_ERR_UNSUPPORTED
-            wcode = dcode = U
-            g_a1 = None
-            if self.sparse_sgb and pooled is not None and saved.get('wc') is not None:
-                def scratch(name, need):
-                    ws = getattr(self, name, None)
-                    if ws is None or ws.numel() < need:
-                        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.dev)
-                        setattr(self, name, ws)
-                    return ws
-                ws = scratch('_sgb_wgrad_ws', lib.stof_train_sgb_wgrad_workspace_bytes(cm))
-                wcode = lib.stof_train_sgb_contract_wgrad(_lib.ptr(gpool), _lib.ptr(arg), _lib.ptr(pooled), _lib.ptr(a1),
-                                                          _lib.ptr(g[sg + 'contract_conv.weight']), _lib.ptr(g[sg + 'contract_conv.bias']),
-                                                          n, L, P, cm, S, 1.0 / self._gscale, _lib.ptr(ws), ws.numel(), st)
-                if wcode != U:
-                    _lib.check(wcode, 'stof_train_sgb_contract_wgrad')
-                if self.sparse_sgb_dgrad:
-                    ws = scratch('_sgb_dgrad_ws', lib.stof_train_sgb_dgrad_workspace_bytes(cm))
-                    g_a1 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
-                    dcode = lib.stof_train_sgb_contract_dgrad(_lib.ptr(gpool), _lib.ptr(arg), _lib.ptr(pooled), _lib.ptr(saved['wc'].contiguous()),
-                                                              _lib.ptr(g_x0), _lib.ptr(g_a1), n, L, P, cm, S, _lib.ptr(ws), ws.numel(), st)
-                    if dcode != U:
-                        _lib.check(dcode, 'stof_train_sgb_contract_dgrad')
-            self.sgb_sparse_taken = (wcode != U and dcode != U)        # bench.py: which route this backward really ran
-            if wcode == U or dcode == U:
-                gc = torch.empty((n, L, cm), dtype=torch.float32, device=self.dev)
-                _lib.check(lib.stof_train_pool_bwd(_lib.ptr(gpool), _lib.ptr(arg), _lib.ptr(c), _lib.ptr(pooled), _lib.ptr(gc), n, L, P, cm, S, st),
-                           'stof_train_pool_bwd')
-                if wcode == U:
-                    self._wgrad(a1, gc, sg + 'contract_conv', 64, cm, 5)
-                if dcode == U:
-                    g_a1 = self._conv(gc, bwd[sg + 'contract_conv'], None, cm, 64, 5, residual=g_x0)
+        g_a1 = self._backward_sgb(saved, g_x0, g, inv) if self.sgb and saved.P else g_x0
+        self._backward_conv1(saved, g_a1, g, inv, dx)
+
+    def _backward_body_sweep(self, saved, g6, g, inv):
+        """conv12^T .. conv2^T as one backward sweep, their weight gradients as one batched launch.  Returns dL/dx_0
+        without the long skip."""
+        # the eleven data-gradient convolutions as ONE backward sweep (stof_train_sweep_bwd), then the weight gradients from
+        # its dumps: tensor j odd = dL/dx_k, k = (11 - j) / 2; j even = dL/d(pre-activation of conv(12 - j))
+        lib, st, p, xs, ys = _lib.lib(), self._st(), saved.p, saved.xs, saved.ys
+        n, L = saved.x.shape
+        blob = self._scratch('_sweep_blob_bwd', lib.stof_train_sweep_blob_bytes(ctypes.byref(saved.desc)))
+        arr = (ctypes.c_void_p * 11)(*[_lib.ptr(p[f'conv{i}.weight'].contiguous()) for i in range(2, 13)])
+        _lib.check(lib.stof_train_sweep_bwd_pack(arr, _lib.ptr(blob), st), 'stof_train_sweep_bwd_pack')
+        dumpb = torch.empty(lib.stof_train_sweep_dump_floats(n, L), dtype=torch.float32, device=self.dev)
+        _lib.check((lib.stof_train_sweep_bwd_split if saved.split else lib.stof_train_sweep_bwd)(
+            ctypes.byref(saved.desc), _lib.ptr(blob), _lib.ptr(g6), _lib.ptr(saved.dump), _lib.ptr(dumpb), n, L, st),
+            'stof_train_sweep_bwd')
+        T = dumpb[:12 * n * L * 64].view(12, n, L, 64)
+        pairs = [(xs[5], g6, 'conv12')]                                             # (input activation, output gradient, layer)
+        for k in range(4, -1, -1):
+            pairs.append((ys[k], T[9 - 2 * k], f'conv{2 * k + 3}'))                 # g_{k+1} = T[11 - 2 (k + 1)]
+            pairs.append((xs[k], T[10 - 2 * k], f'conv{2 * k + 2}'))                # u_k
+        # r4: the eleven k7 weight gradients in ONE launch pair (stof_train_wgrad_batch) instead of eleven launches + eleven
+        # reductions of 58 MB of partials each
+        cnt = len(pairs)
+        ws = self._scratch('_wgrad_batch_ws', lib.stof_train_wgrad_batch_workspace_bytes(cnt, 7))
+        arr = lambda ts: (ctypes.c_void_p * cnt)(*[_lib.ptr(t) for t in ts])
+        operands = (arr([a for a, _, _ in pairs]), arr([d for _, d, _ in pairs]),
+                    arr([g[nm + '.weight'] for _, _, nm in pairs]), arr([g[nm + '.bias'] for _, _, nm in pairs]), cnt)
+        if saved.split:
+            # every x operand is a forward dump tensor (0..10), every dy a backward dump tensor or g6: all split rows
+            all_bits = (1 << cnt) - 1
+            _lib.check(lib.stof_train_wgrad_batch_split(*operands, all_bits, all_bits, n, L, 7, inv, _lib.ptr(ws), ws.numel(), st),
+                       'stof_train_wgrad_batch_split')
         else:
-            g_a1 = g_x0
+            _lib.check(lib.stof_train_wgrad_batch(*operands, n, L, 7, inv, _lib.ptr(ws), ws.numel(), st), 'stof_train_wgrad_batch')
+        return T[11]
+
+    def _backward_body_layers(self, saved, g6, g, inv):
+        """Any num_blocks and body kernel, layer by layer.  Returns dL/dx_0 without the long skip."""
+        # Walking down from the second-last layer: an odd layer i holds the TOTAL gradient gg of its output (its own consumer +
+        # the residual add two layers on); its transposed convolution, masked with lrelu'(v[i-1]), is u = the gradient before
+        # the activation of the even layer i-1; that layer's transposed convolution plus gg (the residual path) is the total
+        # gradient of v[i-2].
+        v, bwd, kb = saved.v, saved.bwd, self.kb
+        m = self.nb - 2                                                           # last layer of the loop (:52)
+        second_last = f'conv{self.nb - 1}'
+        self._wgrad(v[m], g6, g[second_last + '.weight'], g[second_last + '.bias'], 64, 64, kb, inv)
+        if m % 2:
+            gg, u = self._conv(g6, bwd[second_last], None, 64, 64, kb), None        # d/dv[m], v[m] a residual state
+        else:
+            gg, u = None, self._conv(g6, bwd[second_last], None, 64, 64, kb, ACT_LRELU, saved=v[m])
+        for i in range(m, 1, -1):
+            nm = f'conv{i}'
+            if i % 2:
+                self._wgrad(v[i - 1], gg, g[nm + '.weight'], g[nm + '.bias'], 64, 64, kb, inv)
+                u = self._conv(gg, bwd[nm], None, 64, 64, kb, ACT_LRELU, saved=v[i - 1])
+            else:
+                self._wgrad(v[i - 1], u, g[nm + '.weight'], g[nm + '.bias'], 64, 64, kb, inv)
+                gg = self._conv(u, bwd[nm], None, 64, 64, kb, residual=gg)      # (gg None for the loop's last layer)
+        return gg
+
+    def _backward_sgb(self, saved, g_x0, g, inv):
+        """SemiGlobalBlock backward from g_x0 = dL/d(block output): fills the gradients of both convolutions and returns
+        dL/d relu(conv1), the residual path included."""
+        lib, st = _lib.lib(), self._st()
+        (n, L), P, a1, bwd = saved.x.shape, saved.P, saved.a1, saved.bwd
+        e, pooled, arg = saved.e, saved.pooled, saved.arg
+        S, cm = self.scale, self.cmid
+        gw, gb = g[SG + 'contract_conv.weight'], g[SG + 'contract_conv.bias']
+        ge = torch.empty((n, P, 64), dtype=torch.float32, device=self.dev)
+        _lib.check(lib.stof_train_upsample_bwd(_lib.ptr(g_x0), _lib.ptr(e), _lib.ptr(ge), n, L, P, (L - S * P) // 2, S, st),
+                   'stof_train_upsample_bwd')
+        self._wgrad(pooled, ge, g[SG + 'expand_conv.weight'], g[SG + 'expand_conv.bias'], cm, 64, 5, inv)
+        gpool = self._conv(ge, bwd[SG + 'expand_conv'], None, 64, cm, 5)
+        # The gradient behind the max-pool is zero except at ONE row per (waveform, window, channel).  Where the kernels
+        # take the shape, contract_conv's weight gradient and data gradient come straight from those non-zeros
+        # (stof_train_sgb_contract_wgrad / _dgrad); where one answers STOF_ERR_UNSUPPORTED the dense [N, L, cm] gradient is
+        # built (stof_train_pool_bwd) and goes through the layer kernels like every other convolution.
+        U = _lib.STOF_ERR_UNSUPPORTED
+        ws = self._scratch('_sgb_wgrad_ws', lib.stof_train_sgb_wgrad_workspace_bytes(cm))
+        wcode = lib.stof_train_sgb_contract_wgrad(_lib.ptr(gpool), _lib.ptr(arg), _lib.ptr(pooled), _lib.ptr(a1), _lib.ptr(gw),
+                                                  _lib.ptr(gb), n, L, P, cm, S, inv, _lib.ptr(ws), ws.numel(), st)
+        if wcode != U:
+            _lib.check(wcode, 'stof_train_sgb_contract_wgrad')
+        ws = self._scratch('_sgb_dgrad_ws', lib.stof_train_sgb_dgrad_workspace_bytes(cm))
+        g_a1 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
+        dcode = lib.stof_train_sgb_contract_dgrad(_lib.ptr(gpool), _lib.ptr(arg), _lib.ptr(pooled),
+                                                  _lib.ptr(saved.p[SG + 'contract_conv.weight'].contiguous()),
+                                                  _lib.ptr(g_x0), _lib.ptr(g_a1), n, L, P, cm, S, _lib.ptr(ws), ws.numel(), st)
+        if dcode != U:
+            _lib.check(dcode, 'stof_train_sgb_contract_dgrad')
+        self.sgb_sparse_taken = (wcode != U and dcode != U)        # bench.py: which route this backward really ran
+        if wcode == U or dcode == U:
+            gc = torch.empty((n, L, cm), dtype=torch.float32, device=self.dev)
+            _lib.check(lib.stof_train_pool_bwd(_lib.ptr(gpool), _lib.ptr(arg), _lib.ptr(saved.c), _lib.ptr(pooled), _lib.ptr(gc),
+                                               n, L, P, cm, S, st), 'stof_train_pool_bwd')
+            if wcode == U:
+                self._wgrad(a1, gc, gw, gb, 64, cm, 5, inv)
+            if dcode == U:
+                g_a1 = self._conv(gc, bwd[SG + 'contract_conv'], None, cm, 64, 5, residual=g_x0)
+        return g_a1
+
+    def _backward_conv1(self, saved, g_a1, g, inv, dx):
+        """conv1's weight gradient from g_a1 masked with relu'(a1) and, if `dx` is given, d loss / d frame."""
+        lib, st = _lib.lib(), self._st()
+        n, L = saved.x.shape
         ws1 = torch.empty(lib.stof_train_conv1_wgrad_workspace_bytes(), dtype=torch.uint8, device=self.dev)
-        _lib.check(lib.stof_train_conv1_wgrad(_lib.ptr(saved['x']), _lib.ptr(g_a1), _lib.ptr(a1), _lib.ptr(g['conv1.weight']),
-                                              _lib.ptr(g['conv1.bias']), n, L, 1.0 / self._gscale, _lib.ptr(ws1),
-                                              ws1.numel(), st), 'stof_train_conv1_wgrad')
+        _lib.check(lib.stof_train_conv1_wgrad(_lib.ptr(saved.x), _lib.ptr(g_a1), _lib.ptr(saved.a1), _lib.ptr(g['conv1.weight']),
+                                              _lib.ptr(g['conv1.bias']), n, L, inv, _lib.ptr(ws1), ws1.numel(), st),
+                   'stof_train_conv1_wgrad')
         if dx is not None:
-            # d loss / d frame (the reference's autograd yields it for free, models/stofnet.py:45): conv1 transposed on the masked gradient
-            _lib.check(lib.stof_train_conv1_dgrad(_lib.ptr(g_a1), _lib.ptr(a1), _lib.ptr(saved['w1'].contiguous()), _lib.ptr(dx),
-                                                  n, L, 1.0 / self._gscale, st), 'stof_train_conv1_dgrad')
+            # (the reference's autograd yields it for free, models/stofnet.py:45): conv1 transposed on the masked gradient
+            _lib.check(lib.stof_train_conv1_dgrad(_lib.ptr(g_a1), _lib.ptr(saved.a1), _lib.ptr(saved.p['conv1.weight'].contiguous()),
+                                                  _lib.ptr(dx), n, L, inv, st), 'stof_train_conv1_dgrad')
 
 
 class StofNetFunction(torch.autograd.Function):
@@ -454,7 +458,8 @@ class StofNetFunction(torch.autograd.Function):
         if saved is None:
             raise RuntimeError('Trying to backward through the graph a second time: the saved activations of '
                                'StofNet.forward have been freed')
-        n, m = saved['n'], saved['L'] * engine.r
+        n, L = saved.x.shape
+        m = L * engine.r
         with torch.cuda.device(engine.dev):
             dpred = grad_out.detach().reshape(n, m).contiguous().float()
             gscale = 1.0
@@ -463,11 +468,10 @@ class StofNetFunction(torch.autograd.Function):
                 # convolutions.  Scale by the power of two that brings the largest entry to [1, 2) (exact); the
                 # weight-gradient kernels multiply by 1/scale (exact).  One host read per step.
                 # The same read carries the range-guard word of the PREVIOUS backward (below).
-                prev = getattr(engine, '_bwd_overflow', None)
+                prev = engine.take_bwd_overflow()
                 word = dpred.abs().amax().reshape(1)
                 if prev is not None:
                     word = torch.cat([word, prev])
-                    engine._bwd_overflow = None
                 host = word.tolist()
                 amax = host[0]
                 if prev is not None and host[1] != 0.0:
@@ -490,7 +494,7 @@ class StofNetFunction(torch.autograd.Function):
                 off += k
             dx = None
             if ctx.needs_input_grad[0]:                 # d loss / d frame: the reference's autograd yields it (models/stofnet.py:45)
-                dx = torch.empty((n, saved['L']), dtype=torch.float32, device=engine.dev)
+                dx = torch.empty((n, L), dtype=torch.float32, device=engine.dev)
             engine._backward_saved(saved, dpred, g, gscale, dx)
             if engine.prec == 1:
                 # Range guard of the split-fp16 backward, without a second host read: a non-finite gradient zeroes this step's
@@ -502,7 +506,7 @@ class StofNetFunction(torch.autograd.Function):
                     dx.masked_fill_(bad, 0.0)
                 engine._bwd_overflow = bad.float().reshape(1)
         ctx.saved = None
-        return (None if dx is None else dx.view(n, 1, saved['L']), None, None) + tuple(g[name] for name in ctx.names)
+        return (None if dx is None else dx.view(n, 1, L), None, None) + tuple(g[name] for name in ctx.names)
 
 
 class StofNetTrainer(TrainEngine):

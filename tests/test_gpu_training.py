@@ -35,8 +35,7 @@ def test_conv_kernels_vs_torch(dev, prec):
     """generic channel-last conv forward / dgrad / wgrad against F.conv1d and autograd (float64 truth), in the exact
     fp32 mode and the split-fp16 (f16x3) mode of the forward / data-gradient convolutions."""
     import torch.nn.functional as F
-    from stofnet_amd import _lib
-    from stofnet_amd.training import StofNetTrainer
+    from stofnet_amd.training import LayerKernels
     g = torch.Generator().manual_seed(0)
     for cin, cout, K, L in [(64, 64, 7, 150), (64, 512, 5, 100), (512, 64, 5, 70), (64, 10, 3, 90), (10, 64, 3, 65)]:
         x = torch.randn(2, cin, L, generator=g, dtype=torch.float64, requires_grad=True)
@@ -47,10 +46,7 @@ def test_conv_kernels_vs_torch(dev, prec):
         # gradient wrt the pre-activation, then plain conv backward
         pre = F.conv1d(x, w, b, padding=K // 2)
         gx, gw, gb = torch.autograd.grad(pre, [x, w, b], gy)
-        t = StofNetTrainer.__new__(StofNetTrainer)
-        t.dev = dev
-        t.prec = prec
-        t._gscale = 1.0
+        t = LayerKernels(dev, prec)
         xc = x.detach().permute(0, 2, 1).contiguous().float().to(dev)
         wd = w.detach().float().to(dev)
         y_gpu = t._conv(xc, t._repack(wd, False), b.detach().float().to(dev), cin, cout, K, 2)
@@ -58,10 +54,10 @@ def test_conv_kernels_vs_torch(dev, prec):
         gyc = gy.permute(0, 2, 1).contiguous().float().to(dev)
         gx_gpu = t._conv(gyc, t._repack(wd, True), None, cout, cin, K)
         assert relerr(gx_gpu.cpu().numpy(), gx.permute(0, 2, 1).numpy()) < 2e-6
-        t.g = {'w.weight': torch.zeros(cout, cin, K, device=dev), 'w.bias': torch.zeros(cout, device=dev)}
-        t._wgrad(xc, gyc, 'w', cin, cout, K)
-        assert relerr(t.g['w.weight'].cpu().numpy(), gw.numpy()) < 2e-6
-        assert relerr(t.g['w.bias'].cpu().numpy(), gb.numpy()) < 2e-6
+        dw, db = torch.zeros(cout, cin, K, device=dev), torch.zeros(cout, device=dev)
+        t._wgrad(xc, gyc, dw, db, cin, cout, K, 1.0)
+        assert relerr(dw.cpu().numpy(), gw.numpy()) < 2e-6
+        assert relerr(db.cpu().numpy(), gb.numpy()) < 2e-6
 
 @pytest.mark.parametrize('n,L,S,C', [(8, 2000, 80, 512), (1, 2000, 80, 512), (3, 1290, 40, 256), (2, 330, 20, 128)])
 def test_sgb_sparse_contract_weight_gradient_matches_dense_route(dev, n, L, S, C):
