@@ -20,7 +20,7 @@
 // Two arithmetic modes (template PREC):
 //   STOF_PREC_FP32  exact fp32 on v_mfma_f32_32x32x2_f32 (a k-ordered fmaf chain): parity baseline
 //   STOF_PREC_F16X3 operands split x = hi + lo in fp16 (|err| ~ 2^-22 |x|), three
-//                   v_mfma_f32_32x32x16_f16 passes hi*hi + hi*lo + lo*hi, fp32 accumulate
+//                   v_mfma_f32_16x16x32_f16 passes hi*hi + hi*lo + lo*hi, fp32 accumulate
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -44,10 +44,8 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr int LAG_LAST = 34;      // frontier lag of conv_last: 11 convs x 3 + 1
-#ifndef STOF_SGB_NW
-#define STOF_SGB_NW 2          // measured: 2-window tiles with two work-groups per CU beat 4-window tiles by 8 %
-#endif
-constexpr int SGB_NW = STOF_SGB_NW;                    // pooling windows per work-group tile
+// pooling windows per work-group tile; measured: 2-window tiles with two work-groups per CU beat 4-window tiles by 8 %
+constexpr int SGB_NW = 2;
 constexpr int SGB_WAVES_PER_SIMD = (SGB_NW <= 2) ? 2 : 1;   // small tiles: two work-groups share a CU
 constexpr int ROWB = ROWF * 4;    // activation row stride in bytes
 
@@ -80,22 +78,10 @@ __device__ __forceinline__ floatx16 mma_fp32(uint4 a, uint4 b, floatx16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.w, c, 0, 0, 0);
     return c;
 }
-// D += (Ah + Al) * (Bh + Bl) without the lo*lo term, over 16 channels.  (Keeping the two cross
-// terms in an accumulator of their own was measured: no accuracy gain worth its 12 % slowdown.)
-__device__ __forceinline__ floatx16 mma_f16x3(uint4 ah, uint4 al, uint4 bh, uint4 bl, floatx16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(ah), as_h8(bh), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(ah), as_h8(bl), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(al), as_h8(bh), c, 0, 0, 0);
-    return c;
-}
 
-// Byte offset inside an activation row of operand fragment `frag` (see stof_common.h) for the
+// Byte offset inside an fp32 activation row of operand fragment `frag` (see stof_common.h) for the
 // 32-channel half hh and lane half lh.
-template <int PREC>
-__device__ __forceinline__ int act_frag_off(int frag, int hh, int lh) {
-    if constexpr (PREC == STOF_PREC_FP32) return (32 * hh + 8 * frag + 4 * lh) * 4;
-    else return (32 * hh + 16 * (frag >> 1) + 8 * lh) * 2 + 128 * (frag & 1);
-}
+__device__ __forceinline__ int act_frag_off(int frag, int hh, int lh) { return (32 * hh + 8 * frag + 4 * lh) * 4; }
 
 // Store 4 consecutive channels c0..c0+3 of one activation row (row = row base pointer).
 template <int PREC>
@@ -109,17 +95,6 @@ __device__ __forceinline__ void store_act4(char* row, int c0, float4 v) {
         lo[2] = (_Float16)(v.z - (float)hi[2]); lo[3] = (_Float16)(v.w - (float)hi[3]);
         *reinterpret_cast<half4*>(row + 2 * c0) = hi;
         *reinterpret_cast<half4*>(row + 128 + 2 * c0) = lo;
-    }
-}
-template <int PREC>
-__device__ __forceinline__ float4 load_act4(const char* row, int c0) {
-    if constexpr (PREC == STOF_PREC_FP32) {
-        return *reinterpret_cast<const float4*>(row + 4 * c0);
-    } else {
-        const half4 hi = *reinterpret_cast<const half4*>(row + 2 * c0);
-        const half4 lo = *reinterpret_cast<const half4*>(row + 128 + 2 * c0);
-        return make_float4((float)hi[0] + (float)lo[0], (float)hi[1] + (float)lo[1],
-                           (float)hi[2] + (float)lo[2], (float)hi[3] + (float)lo[3]);
     }
 }
 
@@ -198,7 +173,7 @@ struct BodyParams {
     // (virtual) waveform it touches; onsets_finalize_kernel turns them into counts / indices.  y may then be nullptr.
     OnsetPartial* onset_ws;       // [N][onset_slots] (this sub-batch), zeroed by the host side before the launch
     int onset_slots, onset_seg_slots;
-    // training forward (stof_train_sweep, 16x16x32 body only): every layer's output is also written to HBM, channel-last fp32
+    // training forward (stof_train_sweep, split fp16 only): every layer's output is also written to HBM, channel-last fp32
     // [12][N][L][64]: tensor 0 = x0 (relu(conv1) + SemiGlobalBlock), 1..10 = outputs of conv2..conv11 (after leaky ReLU /
     // residual add), 11 = conv12's; followed by >= 2 KiB the kernel may scribble on (rows that are padding)
     float* dump;
@@ -209,7 +184,7 @@ struct BodyParams {
     const float* fwd_dump;
 };
 
-// RF = floats per activation row: ROWF (272 B) for the 32-wide MFMA shapes; 72 (288 B) for the 16x16x32 body, whose
+// RF = floats per activation row: ROWF (272 B) for the fp32 form; 72 (288 B) for the split-fp16 form, whose
 // operand reads (lane = (time row i, k-group q), 16 B at 16 q) are bank-conflict free exactly when the row stride is
 // 2 mod 4 in 16-byte units: unit index mod 16 = 2 i + q + const, and the hardware's ds_read_b128 lane groups pair rows
 // {0-3, 12-15} of one q with rows {4-11} of q + 1 (MI355X_MICROARCH.md, LDS table) -- even values against odd ones.
@@ -224,20 +199,21 @@ struct BodyLds {
     static constexpr size_t BYTES = (size_t)TOTAL * sizeof(float);
 };
 
-constexpr int ROWF16 = 72;        // 288-byte rows of the 16x16x32 body (see BodyLds)
+constexpr int ROWF16 = 72;        // 288-byte rows of the split-fp16 form (see BodyLds)
 
 // BWD: the data-gradient chain of the training step as the same sweep run backwards through the network (stof_train_sweep_bwd):
 // "layer 0" loads dL/dx6 rows from HBM instead of computing conv1, sweep layer j = 1..11 is the transposed convolution of
 // conv(13 - j): j = 1 plain, even j times the leaky-ReLU derivative of the saved activation (sign bytes), odd j >= 3 added to
 // the residual gradient in place; every layer's output goes to HBM for the weight-gradient kernels (DUMP); no conv_last.
-template <int PREC, int S, int RING, int RAWRING, int SHAPE = 32, bool DUMP = false, bool BWD = false>
+template <int PREC, int S, int RING, int RAWRING, bool DUMP = false, bool BWD = false>
 __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) {
-    static_assert(!DUMP || SHAPE == 16, "the training dump lives in the 16x16x32 body");
+    // the MFMA shape follows from the precision: fp32 on 32x32x2 (272-byte rows), split fp16 on 16x16x32 (288-byte rows)
+    constexpr int SHAPE = PREC == STOF_PREC_F16X3 ? 16 : 32;
+    static_assert(!DUMP || PREC == STOF_PREC_F16X3, "the training dump lives in the split-fp16 body");
     static_assert(!BWD || DUMP, "the backward sweep's outputs are its dumps");
     constexpr int NCHUNK_STEP = BWD ? 11 * BODY_CHUNKS_K7 : BODY_NCHUNK;      // weight chunks consumed per sweep step
     static_assert((RING & (RING - 1)) == 0 && (RAWRING & (RAWRING - 1)) == 0, "rings are powers of two");
     static_assert(S % 64 == 0 && S + 36 <= RING && S + 42 <= RAWRING, "ring must hold the live span");
-    static_assert(SHAPE == 32 || (SHAPE == 16 && PREC == STOF_PREC_F16X3), "the 16x16x32 body is a split-fp16 kernel");
     constexpr int RF = SHAPE == 16 ? ROWF16 : ROWF;
     constexpr int ROWB = RF * 4;                 // activation row stride in bytes (shadows the namespace constant)
     using Lds = BodyLds<S, RING, RAWRING, RF>;
@@ -509,7 +485,7 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
             const char* const src = reads_x ? Xr : Yr;
             const int K = last ? 3 : 7, half = K >> 1;
             const int R0 = F - S - layer_lag(j);
-            // conv_last with r <= 16 on one 16-channel tile (split-fp16 modes): shared by both body shapes
+            // conv_last with r <= 16 on one 16-channel tile (split fp16 only)
             auto conv_last16 = [&]() {
                 // conv_last with r <= 16: one 16-channel output tile on v_mfma_f32_16x16x32_f16 instead of two
                 // 32-channel tiles (of which 22+ channels are padding): every wave takes 48 rows of the step,
@@ -602,7 +578,7 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                 STAMP_ADD(2);
             };
             if constexpr (SHAPE == 16) {
-                // ---- split-fp16 layer on v_mfma_f32_16x16x32_f16 (stof_common.h "f16x3 body, 16x16x32").  Wave tile as
+                // ---- split-fp16 layer on v_mfma_f32_16x16x32_f16 (stof_common.h "f16x3 body").  Wave tile as
                 // before (32 output channels x S/2 rows) = 2 M-tiles x NN N-tiles of 16 rows; one chunk = the whole K = 32
                 // of an MFMA: 4 weight fragments (M-tile x hi | lo) and NN x 2 activation fragments feed 6 NN MFMAs.
                 // Lane (i16 = time row of the N-tile, q4 = k-group / accumulator row group): accumulator element e of
@@ -742,10 +718,7 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                             }
                         }
                     }
-#ifndef STOF_TAILC
-#define STOF_TAILC 2
-#endif
-                    constexpr int TAILC = STOF_TAILC, MAINC = BODY_CHUNKS_K7 - TAILC;       // A/B: 0 = no tile-major tail, whole epilogue exposed
+                    constexpr int TAILC = 2, MAINC = BODY_CHUNKS_K7 - TAILC;
 #pragma unroll
                     for (int cc = 0; cc < MAINC; cc += 2) {
                         do_chunk(wf[0], bf0, bf1, cc);
@@ -753,10 +726,7 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                     }
                     // here: wf[0] / wf[1] = the layer's last two chunks, bf0 = activation fragments of chunk MAINC (all tiles);
                     // bf1 is free: it takes the fragments of the last chunk, which land while tile 0's first MFMAs run
-                    if (TAILC > 0) bload(bf1, MAINC + 1);
-#ifdef STOF_STAMP_TAIL_AS_EPI
-                    STAMP_ADD(4);                     // diagnostic: the tile-major tail is then counted with the epilogue (slot 5)
-#endif
+                    bload(bf1, MAINC + 1);
                     // MFMA k (0..11) of N-tile n in the tail: hi*hi, hi*lo, lo*hi of both M-tiles, interleaved so that consecutive
                     // MFMAs never share an accumulator; k < 6 on the second-to-last chunk, k >= 6 on the last one
                     auto tail_mfma = [&](int n, int k) {
@@ -830,14 +800,6 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                         // its own) in program order; one scheduling region per tile with (1 MFMA, 4 VALU) groups.  (Given the
                         // epilogue as four coarse pieces the group-barrier solver clumped the VALU work between two MFMAs.)
                         Epi ep[2];
-                        if constexpr (TAILC == 0) {
-#pragma unroll
-                            for (int n = 0; n < NN; ++n) {
-#pragma unroll
-                                for (int k = 0; k < 12; ++k) epi_slice(ep[0], n, k);
-                            }
-                            return;
-                        }
 #pragma unroll
                         for (int n = 0; n < NN; ++n) {
 #pragma unroll
@@ -851,25 +813,16 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
 #pragma unroll
                                     for (int f = 0; f < FRAGS_PER_CHUNK; ++f) wf[q][f] = wload(c2, f);
                                 }
-#ifdef STOF_TAIL_BLOCK_SCHED
-                                __builtin_amdgcn_sched_barrier(0);      // A/B: pin every (MFMA, slice) pair; measured 0.5 % slower
-#endif
                             }
-#ifndef STOF_TAIL_BLOCK_SCHED
 #pragma unroll
                             for (int i = 0; i < 12; ++i) {
                                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                                 __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
                             }
                             __builtin_amdgcn_sched_barrier(0);
-#endif
                         }
                         c += TAILC;
-#ifdef STOF_STAMP_TAIL_AS_EPI
-                        STAMP_ADD(5);
-#else
                         STAMP_ADD(4);                     // chunk loop (MFMA) incl. the overlapped epilogues
-#endif
 #pragma unroll
                         for (int k = 1; k < 12; ++k) epi_slice(ep[(NN - 1) & 1], NN - 1, k);
                     };
@@ -943,6 +896,7 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                 __syncthreads();
                 STAMP_ADD(2);
             } else {
+            // ---- exact fp32 layer on v_mfma_f32_32x32x2_f32: wave tile = 32 output channels x NT tiles of 32 rows
             // (for conv_last with r <= 32 the waves of the upper output tile multiply zero-padded
             //  weights: free in wall time, and it keeps the chunk body branch-free)
             // accumulators start at the layer's bias (lane (ln, lh) holds channels 32mi + 8gg + 4lh + e)
@@ -964,7 +918,7 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                     const int g = R0 + 32 * (NT * ni + k) + ln + d - half;
                     const char* row = src + (g & (RING - 1)) * ROWB;
 #pragma unroll
-                    for (int f = 0; f < FRAGS_PER_CHUNK; ++f) b[k][f] = ldq(row + act_frag_off<PREC>(f, hh, lh));
+                    for (int f = 0; f < FRAGS_PER_CHUNK; ++f) b[k][f] = ldq(row + act_frag_off(f, hh, lh));
                 }
             };
             // one chunk: MFMAs on (w, bcur) while the ds_reads of the next chunk (bnext) are in flight,
@@ -973,53 +927,27 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                                 uint4 (&bnext)[NT][FRAGS_PER_CHUNK], int cc) {
                 const int c2 = (c + 2 >= BODY_NCHUNK) ? c + 2 - BODY_NCHUNK : c + 2;
                 bload(bnext, cc + 1);          // past the layer's last chunk this reads rows nobody uses
-                if constexpr (PREC == STOF_PREC_FP32) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
+                for (int q = 0; q < 4; ++q) {
 #pragma unroll
-                        for (int k = 0; k < NT; ++k) acc[k] = mma_fp32(w[q], bcur[k][q], acc[k]);
-                        w[q] = wload(c2, q);
-                    }
-                    // interleave: one ds_read behind each of the first MFMAs
+                    for (int k = 0; k < NT; ++k) acc[k] = mma_fp32(w[q], bcur[k][q], acc[k]);
+                    w[q] = wload(c2, q);
+                }
+                // interleave: one ds_read behind each of the first MFMAs
 #pragma unroll
-                    for (int i = 0; i < NT * FRAGS_PER_CHUNK; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                } else {
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                        for (int k = 0; k < NT; ++k)
-                            acc[k] = mma_f16x3(w[2 * ks], w[2 * ks + 1], bcur[k][2 * ks], bcur[k][2 * ks + 1], acc[k]);
-                        w[2 * ks] = wload(c2, 2 * ks);
-                        w[2 * ks + 1] = wload(c2, 2 * ks + 1);
-                    }
-#pragma unroll
-                    for (int i = 0; i < NT * FRAGS_PER_CHUNK; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
+                for (int i = 0; i < NT * FRAGS_PER_CHUNK; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 }
                 ++c;
             };
-            // The chunk loop is fully unrolled (14 chunks for k7 layers, 6 for conv_last): in straight-line
-            // code the compiler counts s_waitcnt vmcnt(N) for the weight prefetch instead of draining it
-            // at a loop header, and the two register sets alternate statically.
+            // The chunk loops are fully unrolled: in straight-line code the compiler counts s_waitcnt vmcnt(N) for the
+            // weight prefetch instead of draining it at a loop header, and the two register sets alternate statically.
             uint4 bf0[NT][FRAGS_PER_CHUNK], bf1[NT][FRAGS_PER_CHUNK];
             bload(bf0, 0);
-            auto run_chunks = [&](auto nchunk_c) {
-                constexpr int NCH = decltype(nchunk_c)::value;
-#pragma unroll
-                for (int cc = 0; cc < NCH; cc += 2) {
-                    do_chunk(wf[0], bf0, bf1, cc);
-                    do_chunk(wf[1], bf1, bf0, cc + 1);
-                }
-            };
             STAMP_ADD(3);                         // layer setup + first activation fragments
-#ifndef STOF_NO_TAIL
             // Tail overlap (k7 layers): the last TAILC chunks run tile-major, so the epilogue of row tile k
-            // (residual add / leaky ReLU, fp16 split, ring store -- VALU + LDS work) is issued in the shadow of
+            // (residual add / leaky ReLU, ring store -- VALU + LDS work) is issued in the shadow of
             // the MFMAs of tile k+1; only the last tile's epilogue stays exposed.  Program order already
             // interleaves the LDS accesses (the compiler cannot reorder ds ops it cannot disambiguate); the
             // sched_group_barriers only slide the VALU work between the MFMAs.
@@ -1038,7 +966,7 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                     int nw, tw;
                     vmap(n0 + nk, tk, nw, tw);
                     tvalid[k] = (g >= 0) && (g < gend) && (tk < L) && (tw >= 0) && (tw < Ltrue);
-                    tslot[k] = (g & (RING - 1)) * ROWB + (32 * mi + 4 * lh) * (PREC == STOF_PREC_FP32 ? 4 : 2);
+                    tslot[k] = (g & (RING - 1)) * ROWB + (32 * mi + 4 * lh) * 4;
                 }
                 constexpr int MAINC = BODY_CHUNKS_K7 - TAILC;
                 uint4 wC[FRAGS_PER_CHUNK], wD[FRAGS_PER_CHUNK];
@@ -1057,16 +985,11 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                     const int g = R0 + 32 * (NT * ni + k) + ln + d - half;
                     const char* row = src + (g & (RING - 1)) * ROWB;
 #pragma unroll
-                    for (int f = 0; f < FRAGS_PER_CHUNK; ++f) b[f] = ldq(row + act_frag_off<PREC>(f, hh, lh));
+                    for (int f = 0; f < FRAGS_PER_CHUNK; ++f) b[f] = ldq(row + act_frag_off(f, hh, lh));
                 };
                 auto mma_tile = [&](const uint4 (&w)[FRAGS_PER_CHUNK], const uint4 (&b)[FRAGS_PER_CHUNK], floatx16& a) {
-                    if constexpr (PREC == STOF_PREC_FP32) {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) a = mma_fp32(w[q], b[q], a);
-                    } else {
-                        a = mma_f16x3(w[0], w[1], b[0], b[1], a);
-                        a = mma_f16x3(w[2], w[3], b[2], b[3], a);
-                    }
+                    for (int q = 0; q < 4; ++q) a = mma_fp32(w[q], b[q], a);
                 };
                 // The tail exists twice, specialised for the two kinds of k7 layers, so that the epilogue pieces carry only
                 // the VALU work their layer needs (in-place layers: old value + add; activation layers: leaky ReLU):
@@ -1075,31 +998,17 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                 static_assert(NT == 3, "validf initialiser assumes 3 row tiles per wave");
                 auto tail = [&](auto inplace_c) {
                     constexpr bool INPL = decltype(inplace_c)::value;
-                    // `old` is the raw LDS image of the 4 channels (fp32: float4; f16x3: hi | lo halves)
+                    // `old` is the raw LDS image of the 4 channels
                     auto epi_load = [&](int k, int gg) -> uint4 {
                         if constexpr (!INPL) return make_uint4(0u, 0u, 0u, 0u);
-                        const char* q = dst + tslot[k];
-                        if constexpr (PREC == STOF_PREC_FP32) {
-                            return ldq(q + 32 * gg);
-                        } else {
-                            const uint2 h = *reinterpret_cast<const uint2*>(q + 16 * gg);
-                            const uint2 l = *reinterpret_cast<const uint2*>(q + 128 + 16 * gg);
-                            return make_uint4(h.x, h.y, l.x, l.y);
-                        }
+                        return ldq(dst + tslot[k] + 32 * gg);
                     };
                     auto epi_store = [&](int k, int gg, uint4 old) {
                         float2v v01 = {acc[k][4 * gg], acc[k][4 * gg + 1]}, v23 = {acc[k][4 * gg + 2], acc[k][4 * gg + 3]};
                         char* q = dst + tslot[k];
                         if constexpr (INPL) {
-                            if constexpr (PREC == STOF_PREC_FP32) {
-                                const float4 o = as_f4(old);
-                                v01[0] += o.x; v01[1] += o.y; v23[0] += o.z; v23[1] += o.w;
-                            } else {
-                                union { uint4 u; half2v h[4]; } c;
-                                c.u = old;
-                                v01 += __builtin_convertvector(c.h[0], float2v) + __builtin_convertvector(c.h[2], float2v);
-                                v23 += __builtin_convertvector(c.h[1], float2v) + __builtin_convertvector(c.h[3], float2v);
-                            }
+                            const float4 o = as_f4(old);
+                            v01[0] += o.x; v01[1] += o.y; v23[0] += o.z; v23[1] += o.w;
                         }
                         const float2v vf = {validf[k], validf[k]};
                         v01 *= vf; v23 *= vf;
@@ -1109,18 +1018,7 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                             v01[0] = fmaxf(v01[0], t01[0]); v01[1] = fmaxf(v01[1], t01[1]);
                             v23[0] = fmaxf(v23[0], t23[0]); v23[1] = fmaxf(v23[1], t23[1]);
                         }
-                        if constexpr (PREC == STOF_PREC_FP32) {
-                            *reinterpret_cast<float4*>(q + 32 * gg) = make_float4(v01[0], v01[1], v23[0], v23[1]);
-                        } else {
-                            const half2v h01 = __builtin_convertvector(v01, half2v), h23 = __builtin_convertvector(v23, half2v);
-                            const float2v d01 = v01 - __builtin_convertvector(h01, float2v);
-                            const float2v d23 = v23 - __builtin_convertvector(h23, float2v);
-                            const half2v l01 = __builtin_convertvector(d01, half2v), l23 = __builtin_convertvector(d23, half2v);
-                            union { half2v h[2]; uint2 u; } ph, pl;
-                            ph.h[0] = h01; ph.h[1] = h23; pl.h[0] = l01; pl.h[1] = l23;
-                            *reinterpret_cast<uint2*>(q + 16 * gg) = ph.u;
-                            *reinterpret_cast<uint2*>(q + 128 + 16 * gg) = pl.u;
-                        }
+                        *reinterpret_cast<float4*>(q + 32 * gg) = make_float4(v01[0], v01[1], v23[0], v23[1]);
                     };
                     uint4 bq[2][FRAGS_PER_CHUNK];
 #pragma unroll
@@ -1139,12 +1037,11 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                                 for (int f = 0; f < FRAGS_PER_CHUNK; ++f) wf[q][f] = wload(c2, f);
                             }
                             if (k > 0) epi_store(k - 1, q, o);
-                            constexpr int NM = PREC == STOF_PREC_FP32 ? 16 : 6;
 #pragma unroll
-                            for (int i = 0; i < NM; ++i) {
+                            for (int i = 0; i < 16; ++i) {                  // the 16 MFMAs of mma_tile
                                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                                 __builtin_amdgcn_sched_group_barrier(0x080, 1, 0);
-                                __builtin_amdgcn_sched_group_barrier(0x002, PREC == STOF_PREC_FP32 ? 2 : 5, 0);
+                                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
                             }
                             __builtin_amdgcn_sched_barrier(0);      // one scheduling region per (tile, chunk)
                         }
@@ -1164,24 +1061,19 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                 STAMP_ADD(2);
                 continue;
             }
-            if constexpr (PREC == STOF_PREC_F16X3) {
-                if (p.last16 != nullptr) {
-                    conv_last16();
-                    continue;
-                }
-            }
-            run_chunks(std::integral_constant<int, BODY_CHUNKS_LAST>{});
-#else
-            if (last) run_chunks(std::integral_constant<int, BODY_CHUNKS_LAST>{});
-            else run_chunks(std::integral_constant<int, BODY_CHUNKS_K7>{});
-#endif
+            // ---- conv_last: 6 chunks, outputs to HBM.  (A lambda, so that the compiler inlines the six chunks as one unit: with
+            // the loop written in place the instruction schedule and SGPR allocation of the whole kernel shift.)
+            auto last_chunks = [&]() {
+#pragma unroll
+                for (int cc = 0; cc < BODY_CHUNKS_LAST; cc += 2) { do_chunk(wf[0], bf0, bf1, cc); do_chunk(wf[1], bf1, bf0, cc + 1); }
+            };
+            last_chunks();
             STAMP_ADD(4);                         // chunk loop (MFMA)
 
-            // ---- epilogue of sweep layer j (the destination ring is not read by this layer)
+            // ---- epilogue: conv_last + SampleShuffle1D: out[n][t*r + k] = conv_last[n][k][t]
             {
                 bool valid[NT];
-                int slot[NT], tt[NT], nn[NT];
-                bool allvalid = true;
+                int tt[NT], nn[NT];
 #pragma unroll
                 for (int k = 0; k < NT; ++k) {
                     const int off = 32 * (NT * ni + k) + ln;
@@ -1189,94 +1081,37 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
                     decode_row(nR, tR, off, nn[k], tt[k]);
                     int nw, tw;
                     vmap(n0 + nn[k], tt[k], nw, tw);
-                    valid[k] = (g >= 0) && (g < gend) && (tt[k] < L) && (tw >= 0) && (tw < Ltrue);
-                    if (last) {                                      // outputs: only the segment's own rows
-                        valid[k] = valid[k] && (tt[k] >= p.halo) && (tt[k] < p.halo + p.seg_len);
-                        nn[k] = nw - n0;
-                        tt[k] = tw;
-                    }
-                    slot[k] = g & (RING - 1);
-                    allvalid = allvalid && valid[k];
+                    // outputs: only the segment's own rows
+                    valid[k] = (g >= 0) && (g < gend) && (tt[k] < L) && (tw >= 0) && (tw < Ltrue) &&
+                               (tt[k] >= p.halo) && (tt[k] < p.halo + p.seg_len);
+                    nn[k] = nw - n0;
+                    tt[k] = tw;
                 }
-                const bool wave_all_valid = __all(allvalid);          // wave-uniform fast path: no masking
-                if (!last) {
-                    char* const dst = (j & 1) ? Yr : Xr;            // odd sweep layers write ring Y
-                    const bool inplace = !(j & 1) || (j == 11);     // residual add: conv3,5,..,11 and conv12
-                    const bool act = (j & 1) && (j != 11);          // leaky ReLU: conv2,4,..,10
-                    float4 v[NT][4];
+                if (p.status != nullptr) {
+                    // A non-finite activation stays so in every output of its receptive field, so checking the
+                    // last layer alone is enough.
+                    bool bad = false;
 #pragma unroll
                     for (int k = 0; k < NT; ++k)
 #pragma unroll
-                        for (int gg = 0; gg < 4; ++gg)
-                            v[k][gg] = make_float4(acc[k][4 * gg], acc[k][4 * gg + 1], acc[k][4 * gg + 2], acc[k][4 * gg + 3]);
-                    if (inplace) {
-                        // all residual reads first (one latency), then the adds
-                        float4 o[NT][4];
+                        for (int e = 0; e < 16; ++e) bad = bad || !(fabsf(acc[k][e]) <= 3.0e38f);
+                    if (__any(bad) && lane == 0) atomicOr(p.status, 1);
+                }
 #pragma unroll
-                        for (int k = 0; k < NT; ++k)
+                for (int k = 0; k < NT; ++k) {
+                    if (!valid[k]) continue;
+                    float* const orow = p.y + ((size_t)(n0 + nn[k]) * Ltrue + tt[k]) * r;
 #pragma unroll
-                            for (int gg = 0; gg < 4; ++gg)
-                                o[k][gg] = load_act4<PREC>(dst + slot[k] * ROWB, 32 * mi + 8 * gg + 4 * lh);
+                    for (int gg = 0; gg < 4; ++gg) {
+                        const int c0 = 32 * mi + 8 * gg + 4 * lh;
+                        if (c0 >= r) continue;
+                        const float vv[4] = {acc[k][4 * gg], acc[k][4 * gg + 1], acc[k][4 * gg + 2], acc[k][4 * gg + 3]};
+                        if ((r & 3) == 0) {
+                            st4(orow + c0, make_float4(vv[0], vv[1], vv[2], vv[3]));
+                        } else {
 #pragma unroll
-                        for (int k = 0; k < NT; ++k)
-#pragma unroll
-                            for (int gg = 0; gg < 4; ++gg) {
-                                v[k][gg].x += o[k][gg].x; v[k][gg].y += o[k][gg].y;
-                                v[k][gg].z += o[k][gg].z; v[k][gg].w += o[k][gg].w;
-                            }
-                    } else if (act) {
-#pragma unroll
-                        for (int k = 0; k < NT; ++k)
-#pragma unroll
-                            for (int gg = 0; gg < 4; ++gg) {
-                                // leaky_relu(v, 0.01) = max(v, 0.01 v)
-                                v[k][gg].x = fmaxf(v[k][gg].x, 0.01f * v[k][gg].x);
-                                v[k][gg].y = fmaxf(v[k][gg].y, 0.01f * v[k][gg].y);
-                                v[k][gg].z = fmaxf(v[k][gg].z, 0.01f * v[k][gg].z);
-                                v[k][gg].w = fmaxf(v[k][gg].w, 0.01f * v[k][gg].w);
-                            }
-                    }
-                    if (!wave_all_valid) {
-#pragma unroll
-                        for (int k = 0; k < NT; ++k)
-                            if (!valid[k]) {
-#pragma unroll
-                                for (int gg = 0; gg < 4; ++gg) v[k][gg] = make_float4(0.f, 0.f, 0.f, 0.f);
-                            }
-                    }
-#pragma unroll
-                    for (int k = 0; k < NT; ++k)
-#pragma unroll
-                        for (int gg = 0; gg < 4; ++gg)
-                            store_act4<PREC>(dst + slot[k] * ROWB, 32 * mi + 8 * gg + 4 * lh, v[k][gg]);
-                } else {
-                    // conv_last + SampleShuffle1D: out[n][t*r + k] = conv_last[n][k][t]
-                    if (p.status != nullptr) {
-                        // An activation beyond the fp16 range (f16x3 mode) turns into inf/NaN and stays so in
-                        // every output of its receptive field, so checking the last layer alone is enough.
-                        bool bad = false;
-#pragma unroll
-                        for (int k = 0; k < NT; ++k)
-#pragma unroll
-                            for (int e = 0; e < 16; ++e) bad = bad || !(fabsf(acc[k][e]) <= 3.0e38f);
-                        if (__any(bad) && lane == 0) atomicOr(p.status, 1);
-                    }
-#pragma unroll
-                    for (int k = 0; k < NT; ++k) {
-                        if (!valid[k]) continue;
-                        float* const orow = p.y + ((size_t)(n0 + nn[k]) * Ltrue + tt[k]) * r;
-#pragma unroll
-                        for (int gg = 0; gg < 4; ++gg) {
-                            const int c0 = 32 * mi + 8 * gg + 4 * lh;
-                            if (c0 >= r) continue;
-                            const float vv[4] = {acc[k][4 * gg], acc[k][4 * gg + 1], acc[k][4 * gg + 2], acc[k][4 * gg + 3]};
-                            if ((r & 3) == 0) {
-                                st4(orow + c0, make_float4(vv[0], vv[1], vv[2], vv[3]));
-                            } else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e)
-                                    if (c0 + e < r) orow[c0 + e] = vv[e];
-                            }
+                            for (int e = 0; e < 4; ++e)
+                                if (c0 + e < r) orow[c0 + e] = vv[e];
                         }
                     }
                 }
@@ -1284,7 +1119,7 @@ __global__ __launch_bounds__(256, 1) void body_sweep_kernel(const BodyParams p) 
             STAMP_ADD(5);                         // epilogue
             __syncthreads();
             STAMP_ADD(2);
-            }   // SHAPE == 32
+            }   // fp32
         }
     }
 #ifdef STOF_STAMPS
@@ -1316,11 +1151,11 @@ struct SgbParams {
     unsigned char* arg;    // training (ARG): [N][P][512] row offset (0..79) of the window's FIRST maximum, for the pool's backward
 };
 
-template <int PREC, int NW, int SHAPE = 32, bool ARG = false>
+template <int PREC, int NW, bool ARG = false>
 __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_kernel(const SgbParams p) {
-    static_assert(!ARG || SHAPE == 16, "the arg-max output lives in the 16x16x32 form");
+    constexpr int SHAPE = PREC == STOF_PREC_F16X3 ? 16 : 32;      // MFMA shape and row stride follow the precision, as in the body
+    static_assert(!ARG || PREC == STOF_PREC_F16X3, "the arg-max output lives in the split-fp16 form");
     static_assert(NW % 2 == 0, "80*NW must be a multiple of 32");
-    static_assert(SHAPE == 32 || (SHAPE == 16 && PREC == STOF_PREC_F16X3), "the 16x16x32 form is a split-fp16 kernel");
     constexpr int ROWS = SGB_SCALE * NW;          // output rows of the tile
     constexpr int MT = ROWS / 32;
     constexpr int TR = ROWS + 4;                  // conv1 rows needed (k5: +-2)
@@ -1382,7 +1217,7 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
 
     int c = 0;
     if constexpr (SHAPE == 16) {
-        // ---- split-fp16 on v_mfma_f32_16x16x32_f16 (stof_common.h "f16x3 SemiGlobalBlock chunks, 16x16x32").  Time stays on
+        // ---- split-fp16 on v_mfma_f32_16x16x32_f16 (stof_common.h "f16x3 SemiGlobalBlock chunks").  Time stays on
         // the M axis: D[time 4q+e][channel j] of lane (j = lane & 15, q = lane >> 4), the wave's 32 channels are 2 N-tiles,
         // the 80 NW rows are 5 NW M-tiles of 16 -- a pooling window is exactly 5 M-tiles, so the pool is an in-lane max
         // over accumulator registers plus two cross-lane steps (q).  Pipeline unit = the 5 M-tiles of one window against a
@@ -1496,8 +1331,8 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
                 }
             }
         }
-        return;
-    }
+    } else {
+    // ---- exact fp32 on v_mfma_f32_32x32x2_f32
     for (int ocb = 0; ocb < 4; ++ocb) {
         floatx16 acc[MT];
 #pragma unroll
@@ -1505,52 +1340,34 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
 
-        // Pipeline unit = one k-step of a chunk (f16x3: 16 channels, fragments {hi, lo}; fp32: one
-        // 8-channel fragment): while the unit's MT x (3 | 4) MFMAs run, the activation fragments
-        // (MFMA A operand, time on M) of the next unit are read from LDS into the other register set.
-        constexpr int UPC = (PREC == STOF_PREC_FP32) ? 4 : 2;        // units per chunk
-        constexpr int FPU = FRAGS_PER_CHUNK / UPC;                    // fragments per unit
+        // Pipeline unit = one 8-channel fragment of a chunk: while the unit's MT x 4 MFMAs run, the activation
+        // fragments (MFMA A operand, time on M) of the next unit are read from LDS into the other register set.
+        constexpr int UPC = FRAGS_PER_CHUNK;                          // units per chunk
         constexpr int NUNIT = 10 * UPC;                               // per 128-channel output block
-        auto aload = [&](uint4 (&a)[MT][FPU], int uu) {
+        auto aload = [&](uint4 (&a)[MT], int uu) {
             const int cc = uu / UPC, sub = uu % UPC;
             const int d = cc >> 1, hh = cc & 1;
             const char* arow = act + (ln + d) * ROWB;
 #pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int i = 0; i < FPU; ++i)
-                    a[m][i] = ldq(arow + 32 * m * ROWB + act_frag_off<PREC>(sub * FPU + i, hh, lh));
+            for (int m = 0; m < MT; ++m) a[m] = ldq(arow + 32 * m * ROWB + act_frag_off(sub, hh, lh));
         };
-        auto do_unit = [&](uint4 (&acur)[MT][FPU], uint4 (&anext)[MT][FPU], int uu) {
+        auto do_unit = [&](uint4 (&acur)[MT], uint4 (&anext)[MT], int uu) {
             const int cc = uu / UPC, sub = uu % UPC;
             uint4 (&w)[FRAGS_PER_CHUNK] = wf[cc & 1];
             const int c2 = (c + 2 < SGB_NCHUNK) ? c + 2 : 0;     // past the end: harmless reload of chunk 0
             aload(anext, uu + 1 < NUNIT ? uu + 1 : 0);          // the next output block starts with the same rows
-            if constexpr (PREC == STOF_PREC_FP32) {
 #pragma unroll
-                for (int m = 0; m < MT; ++m) acc[m] = mma_fp32(acur[m][0], w[sub], acc[m]);
-                w[sub] = wload(c2, sub);
+            for (int m = 0; m < MT; ++m) acc[m] = mma_fp32(acur[m], w[sub], acc[m]);
+            w[sub] = wload(c2, sub);
 #pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-            } else {
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-                    acc[m] = mma_f16x3(acur[m][0], acur[m][1], w[2 * sub], w[2 * sub + 1], acc[m]);
-                w[2 * sub] = wload(c2, 2 * sub);
-                w[2 * sub + 1] = wload(c2, 2 * sub + 1);
-#pragma unroll
-                for (int i = 0; i < MT * FPU; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
+            for (int i = 0; i < MT; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
             if (sub == UPC - 1) ++c;
             __builtin_amdgcn_sched_barrier(0);      // one scheduling region per unit (keeps the igroup solver fast)
         };
-        uint4 af0[MT][FPU], af1[MT][FPU];
+        uint4 af0[MT], af1[MT];
         if (ocb == 0) aload(af0, 0);
 #pragma unroll
         for (int uu = 0; uu < NUNIT; uu += 2) {
@@ -1580,6 +1397,7 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
                 p.pooled[((size_t)n * p.P + w0 + w) * NF_SGB + oc] = mval;
         }
     }
+    }   // fp32
 }
 
 // get_maxima_positions in arg-max mode from the tile partials of one sub-batch: one wavefront per waveform.
@@ -1644,7 +1462,7 @@ struct OnsetArgs {                        // non-null ws: stof_forward_onsets
 };
 constexpr int64_t SUB_BATCH = 4096;      // rows whose SGB maps share one workspace
 
-constexpr size_t sgb_lds_bytes(int rowf = ROWF) {
+constexpr size_t sgb_lds_bytes(int rowf) {
     return (size_t)((SGB_SCALE * SGB_NW + 4) * rowf + SGB_SCALE * SGB_NW + 12) * sizeof(float);
 }
 
@@ -1666,41 +1484,26 @@ int launch_forward(const stof_net_desc* desc, const void* packed_dev, const floa
     const float* body = base + off;    off += (uint64_t)BODY_NCHUNK * BODY_CHUNK_F;
     const float* last16 = nullptr;
     if (PREC == STOF_PREC_F16X3 && r <= 16) { last16 = base + off; off += LAST16_F; }
-    static const bool no_last16 = getenv("STOF_NO_LAST16") != nullptr;     // diagnostic A/B switch
-    const float* last16_use = no_last16 ? nullptr : last16;
     const float* cbias = base + off;   off += NF_SGB;
     const float* cchunks = base + off; off += (uint64_t)SGB_NCHUNK * SGB_CHUNK_F;
     const float* ew = base + off;      off += 5ull * NF_SGB * NF;
     const float* ebias = base + off;
 
-    // split-fp16 body: 16x16x32 MFMA form unless STOF_BODY16=0 (the packed blob carries the matching fragment order)
-    static const bool body16 = PREC == STOF_PREC_F16X3 && body16_enabled();
-    // r4: two-pass tile-major layers (body_p2.h) unless STOF_BODY_P2=0 (the r3 chunk-major kernel, kept for A/B runs)
-    static const bool body_p2 = body16 && body_p2_enabled();
-    constexpr int SHAPE_FAST = PREC == STOF_PREC_F16X3 ? 16 : 32;
-    using Lds = BodyLds<BODY_S, BODY_RING, BODY_RAWRING>;
-    using Lds16 = BodyLds<BODY_S, BODY_RING, BODY_RAWRING, ROWF16>;
-    const size_t body_p2_bytes = Lds16::BYTES + BODY_P2_C1F * sizeof(float);
-    const size_t body_lds_bytes = body_p2 ? body_p2_bytes : body16 ? Lds16::BYTES : Lds::BYTES;
-    static LdsLimitOnce body_lds, body16_lds, body_p2_lds, sgb_lds;     // one per template instantiation (PREC)
-    if (body_p2) {                                   // (+ the r3 kernel: waveforms shorter than 2 S rows go to it, see body_p2_rows_ok)
-        if (int st = body_p2_lds.ensure(reinterpret_cast<const void*>(&body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING>),
-                                        (int)body_p2_bytes)) return st;
-        if (int st = body16_lds.ensure(reinterpret_cast<const void*>(&body_sweep_kernel<PREC, BODY_S, BODY_RING, BODY_RAWRING, SHAPE_FAST>),
-                                       (int)Lds16::BYTES)) return st;
-    } else if (body16) {
-        if (int st = body16_lds.ensure(reinterpret_cast<const void*>(&body_sweep_kernel<PREC, BODY_S, BODY_RING, BODY_RAWRING, SHAPE_FAST>),
-                                       (int)Lds16::BYTES)) return st;
-    } else if (int st = body_lds.ensure(reinterpret_cast<const void*>(&body_sweep_kernel<PREC, BODY_S, BODY_RING, BODY_RAWRING>),
-                                        (int)Lds::BYTES)) return st;
-    // the SemiGlobalBlock contract kernel follows the body's MFMA shape (and the blob its fragment order)
-    static LdsLimitOnce sgb16_lds;
-    const size_t sgb_bytes = body16 ? sgb_lds_bytes(ROWF16) : sgb_lds_bytes();
-    if (body16) {
-        if (int st = sgb16_lds.ensure(reinterpret_cast<const void*>(&sgb_contract_pool_kernel<PREC, SGB_NW, SHAPE_FAST>), (int)sgb_bytes))
-            return st;
-    } else if (int st = sgb_lds.ensure(reinterpret_cast<const void*>(&sgb_contract_pool_kernel<PREC, SGB_NW>), (int)sgb_bytes))
-        return st;
+    // split fp16: two-pass tile-major layers (body_p2.h) unless STOF_BODY_P2=0 (the r3 chunk-major kernel alone, for A/B runs);
+    // waveforms shorter than 2 S stream rows go to the r3 kernel either way (body_p2_rows_ok)
+    static const bool body_p2 = PREC == STOF_PREC_F16X3 && body_p2_enabled();
+    constexpr int RF = PREC == STOF_PREC_F16X3 ? ROWF16 : ROWF;
+    using Lds = BodyLds<BODY_S, BODY_RING, BODY_RAWRING, RF>;
+    const size_t body_p2_bytes = Lds::BYTES + BODY_P2_C1F * sizeof(float);
+    const auto body_kernel = &body_sweep_kernel<PREC, BODY_S, BODY_RING, BODY_RAWRING>;
+    const auto body_p2_kernel = &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING>;
+    const auto sgb_kernel = &sgb_contract_pool_kernel<PREC, SGB_NW>;
+    const size_t sgb_bytes = sgb_lds_bytes(RF);
+    static LdsLimitOnce body_lds, body_p2_lds, sgb_lds;     // one set per template instantiation (PREC)
+    if (int st = body_lds.ensure(reinterpret_cast<const void*>(body_kernel), (int)Lds::BYTES)) return st;
+    if (body_p2)
+        if (int st = body_p2_lds.ensure(reinterpret_cast<const void*>(body_p2_kernel), (int)body_p2_bytes)) return st;
+    if (int st = sgb_lds.ensure(reinterpret_cast<const void*>(sgb_kernel), (int)sgb_bytes)) return st;
     const int ncu = device_cu_count();
 
     for (int64_t b0 = 0; b0 < N; b0 += SUB_BATCH) {
@@ -1720,12 +1523,7 @@ int launch_forward(const stof_net_desc* desc, const void* packed_dev, const floa
             sp.tiles_per_wf = (int)((P + SGB_NW - 1) / SGB_NW);
             sp.run_if = run_if;
             sp.arg = nullptr;
-            if (body16)
-                hipLaunchKernelGGL((sgb_contract_pool_kernel<PREC, SGB_NW, SHAPE_FAST>), dim3((unsigned)(nb * sp.tiles_per_wf)),
-                                   dim3(256), sgb_bytes, stream, sp);
-            else
-                hipLaunchKernelGGL((sgb_contract_pool_kernel<PREC, SGB_NW>), dim3((unsigned)(nb * sp.tiles_per_wf)),
-                                   dim3(256), sgb_bytes, stream, sp);
+            hipLaunchKernelGGL(sgb_kernel, dim3((unsigned)(nb * sp.tiles_per_wf)), dim3(256), sgb_bytes, stream, sp);
             if (ev) (void)hipEventRecord(static_cast<hipEvent_t>(events[1]), stream);
             {
                 const int st = stof::launch_conv_cl(pooled, ew, ebias, nullptr, nullptr, sgb, 1, nb * (P + 2), NF_SGB, NF, 5,
@@ -1739,7 +1537,7 @@ int launch_forward(const stof_net_desc* desc, const void* packed_dev, const floa
         }
         BodyParams bp;
         bp.x = xb; bp.sgb = (has_sgb && P > 0) ? sgb : nullptr; bp.y = yb;
-        bp.c1 = c1; bp.bias = bias; bp.chunks = body; bp.last16 = last16_use;
+        bp.c1 = c1; bp.bias = bias; bp.chunks = body; bp.last16 = last16;
         bp.N = (int)nb; bp.L = (int)L; bp.r = r; bp.P = (int)P; bp.rem_half = (int)(rem / 2);
         bp.stamps = nullptr;
         bp.dump = nullptr; bp.dump_stride = 0;
@@ -1786,14 +1584,9 @@ int launch_forward(const stof_net_desc* desc, const void* packed_dev, const floa
         bp.wf_per_wg = (int)((nv + wgs - 1) / wgs);
         wgs = (nv + bp.wf_per_wg - 1) / bp.wf_per_wg;
         if (body_p2 && body_p2_rows_ok(bp.seg_len, bp.halo))
-            hipLaunchKernelGGL((body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING>), dim3((unsigned)wgs), dim3(256),
-                               body_p2_bytes, stream, bp);
-        else if (body16)
-            hipLaunchKernelGGL((body_sweep_kernel<PREC, BODY_S, BODY_RING, BODY_RAWRING, SHAPE_FAST>), dim3((unsigned)wgs), dim3(256),
-                               Lds16::BYTES, stream, bp);
+            hipLaunchKernelGGL(body_p2_kernel, dim3((unsigned)wgs), dim3(256), body_p2_bytes, stream, bp);
         else
-            hipLaunchKernelGGL((body_sweep_kernel<PREC, BODY_S, BODY_RING, BODY_RAWRING>), dim3((unsigned)wgs), dim3(256),
-                               body_lds_bytes, stream, bp);
+            hipLaunchKernelGGL(body_kernel, dim3((unsigned)wgs), dim3(256), Lds::BYTES, stream, bp);
         if (ev) (void)hipEventRecord(static_cast<hipEvent_t>(events[3]), stream);
         if (onsets != nullptr)
             hipLaunchKernelGGL(onsets_finalize_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, stream, onsets->ws,
@@ -1878,7 +1671,7 @@ extern "C" int stof_forward_onsets(const stof_net_desc* desc, const void* packed
                                    void* workspace, size_t workspace_bytes, void* stream, int32_t* status_dev) {
     if (!desc || !counts || (!idx && idx_cap > 0) || idx_cap < 0 || window_size < 0) return STOF_ERR_BAD_ARG;
     // the fused picker lives in the 16-channel conv_last tile of the split-fp16 sweep
-    if (desc->precision != STOF_PREC_F16X3 || desc->upsample_factor > 16 || L < 32 || getenv("STOF_NO_LAST16") != nullptr)
+    if (desc->precision != STOF_PREC_F16X3 || desc->upsample_factor > 16 || L < 32)
         return STOF_ERR_UNSUPPORTED;
     if (N > 0 && L > 0 && (!workspace || workspace_bytes < stof_forward_onsets_workspace_bytes(desc, N, L))) return STOF_ERR_WORKSPACE;
     OnsetArgs oa;
@@ -2060,7 +1853,7 @@ static int train_sweep_impl(const stof_net_desc* desc, const void* blob_dev, con
     if (split && !p2) return STOF_ERR_UNSUPPORTED;              // split-row dumps exist in the two-pass kernel only
     auto kernel = split ? &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, false, true>
                   : p2  ? &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, false>
-                        : &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, 16, true, false>;
+                        : &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, true, false>;
     const size_t lds_bytes = Lds16::BYTES + (p2 ? BODY_P2_C1F * sizeof(float) : 0);
     static LdsLimitOnce lds[2];
     if (int st = lds[split ? 1 : 0].ensure(reinterpret_cast<const void*>(kernel), (int)lds_bytes)) return st;
@@ -2081,7 +1874,7 @@ static int train_sweep_impl(const stof_net_desc* desc, const void* blob_dev, con
     if (int st = train_sweep_geometry(desc, bp, N, L, &wgs)) return st;
     if (p2 && !body_p2_rows_ok(bp.seg_len, bp.halo)) {            // short waveforms: the r3 kernel (fp32 dumps only)
         if (split) return STOF_ERR_UNSUPPORTED;
-        auto k3 = &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, 16, true, false>;
+        auto k3 = &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, true, false>;
         static LdsLimitOnce lds3;
         if (int st = lds3.ensure(reinterpret_cast<const void*>(k3), (int)Lds16::BYTES)) return st;
         hipLaunchKernelGGL(k3, dim3((unsigned)wgs), dim3(256), Lds16::BYTES, stream, bp);
@@ -2146,7 +1939,7 @@ extern "C" int stof_train_sgb_contract_pool(const float* conv1_w, const float* c
     a.c1w = conv1_w; a.c1b = conv1_b; a.cw = contract_w; a.cb = contract_b; a.blob = static_cast<float*>(blob_dev);
     const long long total = 640 + NF_SGB + (long long)SGB_NCHUNK * SGB_CHUNK_F * 2;
     hipLaunchKernelGGL(sgb_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a);
-    auto kernel = &sgb_contract_pool_kernel<STOF_PREC_F16X3, SGB_NW, 16, true>;
+    auto kernel = &sgb_contract_pool_kernel<STOF_PREC_F16X3, SGB_NW, true>;
     static LdsLimitOnce lds;
     if (int st = lds.ensure(reinterpret_cast<const void*>(kernel), (int)sgb_lds_bytes(ROWF16))) return st;
     SgbParams sp;
@@ -2210,7 +2003,7 @@ static int train_sweep_bwd_impl(const stof_net_desc* desc, const void* blob_dev,
     if (split && !p2) return STOF_ERR_UNSUPPORTED;
     auto kernel = split ? &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, true, true>
                   : p2  ? &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, true>
-                        : &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, 16, true, true>;
+                        : &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, true, true>;
     const size_t lds_bytes = Lds16::BYTES + (p2 ? BODY_P2_C1F * sizeof(float) : 0);
     static LdsLimitOnce lds[2];
     if (int st = lds[split ? 1 : 0].ensure(reinterpret_cast<const void*>(kernel), (int)lds_bytes)) return st;
@@ -2230,7 +2023,7 @@ static int train_sweep_bwd_impl(const stof_net_desc* desc, const void* blob_dev,
     if (int st = train_sweep_geometry(desc, bp, N, L, &wgs)) return st;
     if (p2 && !body_p2_rows_ok(bp.seg_len, bp.halo)) {            // short waveforms: the r3 kernel (fp32 dumps only)
         if (split) return STOF_ERR_UNSUPPORTED;
-        auto k3 = &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, 16, true, true>;
+        auto k3 = &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, true, true>;
         static LdsLimitOnce lds3;
         if (int st = lds3.ensure(reinterpret_cast<const void*>(k3), (int)Lds16::BYTES)) return st;
         hipLaunchKernelGGL(k3, dim3((unsigned)wgs), dim3(256), Lds16::BYTES, stream, bp);

@@ -13,7 +13,7 @@ static void layout(const stof_net_desc* d, PackedHeader* h) {
     h->r = d->upsample_factor;
     h->sgs = d->semi_global_scale;
     h->precision = d->precision;
-    h->pad0 = (d->precision == STOF_PREC_F16X3 && body16_enabled()) ? 1 : 0;     // body chunk layout: 1 = 16x16x32 fragments
+    h->pad0 = d->precision == STOF_PREC_F16X3 ? 1 : 0;     // body chunk layout: 1 = 16x16x32 fragments
     uint64_t off = sizeof(PackedHeader) / sizeof(float);
     h->off_c1 = off;      off += 64 * 10;
     h->off_bias = off;    off += 13 * 64;
@@ -37,34 +37,22 @@ static int check_desc(const stof_net_desc* d) {
     return STOF_OK;
 }
 
-// One chunk = FRAGS_PER_CHUNK fragments x `tiles` output tiles of 32 channels, fragment-major:
+// One fp32 chunk = FRAGS_PER_CHUNK fragments x `tiles` output tiles of 32 channels, fragment-major:
 // float offset ((frag * tiles + tile) * 64 + lane) * 4.  Rows >= co are zero (conv_last padding).
-static void pack_chunk(float* dst, int tiles, int row0, const float* w, int co, int ci, int K, int tap, int hh,
-                       int precision) {
+static void pack_chunk(float* dst, int tiles, int row0, const float* w, int co, int ci, int K, int tap, int hh) {
     for (int frag = 0; frag < FRAGS_PER_CHUNK; ++frag)
         for (int tile = 0; tile < tiles; ++tile)
             for (int lane = 0; lane < 64; ++lane) {
                 const int m = row0 + 32 * tile + (lane & 31), hl = lane >> 5;
                 float* out = dst + ((size_t)(frag * tiles + tile) * 64 + lane) * 4;
-                if (precision == STOF_PREC_FP32) {
-                    for (int e = 0; e < 4; ++e) {
-                        const int c = 32 * hh + 8 * frag + 4 * hl + e;
-                        out[e] = m < co ? w[((size_t)m * ci + c) * K + tap] : 0.f;
-                    }
-                } else {
-                    const int ks = frag >> 1, part = frag & 1;
-                    _Float16* oh = reinterpret_cast<_Float16*>(out);
-                    for (int e = 0; e < 8; ++e) {
-                        const int c = 32 * hh + 16 * ks + 8 * hl + e;
-                        const float v = m < co ? w[((size_t)m * ci + c) * K + tap] : 0.f;
-                        const _Float16 hi = (_Float16)v;
-                        oh[e] = part == 0 ? hi : (_Float16)(v - (float)hi);
-                    }
+                for (int e = 0; e < 4; ++e) {
+                    const int c = 32 * hh + 8 * frag + 4 * hl + e;
+                    out[e] = m < co ? w[((size_t)m * ci + c) * K + tap] : 0.f;
                 }
             }
 }
 
-// Body chunk of the split-fp16 sweep on v_mfma_f32_16x16x32_f16 (stof_common.h, "f16x3 body, 16x16x32"): 2 output blocks
+// Body chunk of the split-fp16 sweep on v_mfma_f32_16x16x32_f16 (stof_common.h, "f16x3 body"): 2 output blocks
 // of 32 channels x 4 fragments (M-tile m = 0, 1 x hi | lo), float offset ((frag * 2 + block) * 64 + lane) * 4.
 static void pack_chunk16(float* dst, const float* w, int co, int ci, int K, int tap, int hh) {
     for (int frag = 0; frag < FRAGS_PER_CHUNK; ++frag)
@@ -142,8 +130,8 @@ extern "C" int stof_pack_weights(const stof_net_desc* desc, const float* const* 
         const int co = last ? r : NF;
         for (int t = 0; t < K; ++t)
             for (int hh = 0; hh < 2; ++hh) {
-                if (desc->precision == STOF_PREC_F16X3 && body16_enabled()) pack_chunk16(ck, w, co, NF, K, t, hh);
-                else pack_chunk(ck, 2, 0, w, co, NF, K, t, hh, desc->precision);
+                if (desc->precision == STOF_PREC_F16X3) pack_chunk16(ck, w, co, NF, K, t, hh);
+                else pack_chunk(ck, 2, 0, w, co, NF, K, t, hh);
                 ck += BODY_CHUNK_F;
             }
     }
@@ -171,8 +159,8 @@ extern "C" int stof_pack_weights(const stof_net_desc* desc, const float* const* 
         for (int ocb = 0; ocb < 4; ++ocb)
             for (int t = 0; t < 5; ++t)
                 for (int hh = 0; hh < 2; ++hh) {
-                    if (desc->precision == STOF_PREC_F16X3 && body16_enabled()) pack_chunk16_sgb(cc, 128 * ocb, wc, NF, 5, t, hh);
-                    else pack_chunk(cc, 4, 128 * ocb, wc, NF_SGB, NF, 5, t, hh, desc->precision);
+                    if (desc->precision == STOF_PREC_F16X3) pack_chunk16_sgb(cc, 128 * ocb, wc, NF, 5, t, hh);
+                    else pack_chunk(cc, 4, 128 * ocb, wc, NF_SGB, NF, 5, t, hh);
                     cc += SGB_CHUNK_F;
                 }
         const float* we = params[28];                                   // (64, 512, 5)

@@ -12,28 +12,25 @@ constexpr int NF_SGB = 512;       // feat_scale * out_channels = 8 * 64 (models/
 constexpr int SGB_SCALE = 80;     // semi_global_scale of every shipped checkpoint
 constexpr int GAP = 4;            // zero rows between waveforms in the body sweep (= conv1 padding)
 
-// LDS geometry.  An activation row is 256 B of payload padded to 272 B (68 floats) so that the
-// 16 lanes of a ds_read_b128 group (consecutive time rows, same channel offset) fall on 16
-// distinct 4-bank groups.  Payload per precision mode:
-//   fp32  : 64 channels x fp32
-//   f16x3 : 64 channels x fp16 "hi" | 64 channels x fp16 "lo"   (x = hi + lo to ~2^-22)
+// LDS geometry.  An activation row is 256 B of payload, padded so that the 16 lanes of a ds_read_b128 group fall on 16
+// distinct 4-bank groups.  Payload and stride per precision mode:
+//   fp32  : 64 channels x fp32, 272-byte rows (ROWF = 68 floats; lanes = consecutive time rows, same channel offset)
+//   f16x3 : 64 channels x fp16 "hi" | 64 channels x fp16 "lo" (x = hi + lo to ~2^-22), 288-byte rows (convstack.hip, BodyLds)
 constexpr int ROWF = 68;
 
 // Weights are stored in MFMA-fragment order so that a wave fetches one operand fragment with a
 // single fully coalesced 1-KiB load (lane l gets bytes [16 l, 16 l + 16)) straight into the
 // registers the MFMA reads -- no LDS staging.  A "chunk" is one (layer, tap, 32-input-channel
-// half); it holds FRAGS_PER_CHUNK fragments for each 32-wide output-channel tile:
-//   fp32  : fragment q (0..3)        : lane (m = l&31, h = l>>5) -> W[m][32*half + 8q + 4h + 0..3]   (4 x fp32)
-//   f16x3 : fragment 2*ks + part     : lane (m, h) -> part(W[m][32*half + 16ks + 8h + 0..7])         (8 x fp16)
-//           part 0 = hi, 1 = lo
-//   f16x3 body, 16x16x32 (r3, the default; STOF_BODY16=0 in the environment of BOTH the packing and the launching process selects
-//           the 32x32x16 form above for A/B runs): the body sweep multiplies on v_mfma_f32_16x16x32_f16 -- on this part the
-//           16x16x32 shape sustains a ~12 % higher clock than 32x32x16 under the power cap at equal cycles per flop
-//           (tools/micro/mfma_shape_lds.hip, profiles/r03_mfma_shape_lds.jsonl).  A chunk is the whole K = 32 of one MFMA:
-//           fragment 2*m + part : lane (i = l&15, q = l>>4) -> part(W[body16_out_channel(block, m, i)][32*half + 8q + 0..7])
+// half); it holds FRAGS_PER_CHUNK fragments for each 32-wide output-channel tile.  Two forms, one per precision:
+//   fp32, v_mfma_f32_32x32x2_f32 (body and SemiGlobalBlock): a fragment is 8 input channels,
+//           fragment q (0..3) : lane (m = l&31, h = l>>5) -> W[m][32*half + 8q + 4h + 0..3]   (4 x fp32)
+//   f16x3 body, v_mfma_f32_16x16x32_f16: on this part the 16x16x32 shape sustains a ~12 % higher clock than 32x32x16
+//           under the power cap at equal cycles per flop (tools/micro/mfma_shape_lds.hip, profiles/r03_mfma_shape_lds.jsonl).
+//           A chunk is the whole K = 32 of one MFMA; part 0 = hi, 1 = lo:
+//           fragment 2*m + part : lane (i = l&15, q = l>>4) -> part(W[body16_out_channel(block, m, i)][32*half + 8q + 0..7])   (8 x fp16)
 //           The output-channel order inside a 32-channel block is permuted so that the accumulator lane (column = time row,
 //           q) of M-tiles m = 0, 1 holds the 8 CONSECUTIVE channels 8q .. 8q+7: one 16-byte LDS store per lane and row.
-//   f16x3 SemiGlobalBlock chunks, 16x16x32 (with the body): the weights are the B operand (N = output channel), time is on M:
+//   f16x3 SemiGlobalBlock chunks, v_mfma_f32_16x16x32_f16: the weights are the B operand (N = output channel), time is on M:
 //           fragment 2*nt + part of wave tile `tile` : lane (j = l&15, q = l>>4) -> part(W[32 tile + 16 nt + j][32*half + 8q + 0..7])
 constexpr int FRAGS_PER_CHUNK = 4;
 constexpr int FRAG_F = 256;                                   // floats per fragment (1 KiB)
@@ -69,10 +66,6 @@ constexpr uint32_t PACK_MAGIC = 0x464F5453u;
 // 16x16x32 body: output channel held by row i (0..15) of M-tile m (0, 1) of the 32-channel block `block`:
 // accumulator element e of lane (col, q) is row 4q + e, i.e. channel 32 block + 8q + 4m + e.
 constexpr int body16_out_channel(int block, int m, int i) { return 32 * block + 8 * (i >> 2) + 4 * m + (i & 3); }
-inline bool body16_enabled() {
-    const char* e = getenv("STOF_BODY16");
-    return e == nullptr || e[0] != '0';
-}
 // r4: the 16x16x32 body sweeps its k7 layers two-pass tile-major (body_p2.h); STOF_BODY_P2=0 selects the r3 chunk-major kernel
 // on the same packed blob (A/B runs)
 inline bool body_p2_enabled() {

@@ -2074,8 +2074,7 @@ int launch_conv_cl(const float* x, const float* w, const float* bias, const floa
     const int64_t tiles = N * p.tiles_per_wf;
     if (tiles > 0x7fffffffLL || N * L > 0x7fffffffLL) return STOF_ERR_UNSUPPORTED;
     p.total_tiles = (int)tiles;
-    static const bool fast16 = stof::body16_enabled();
-    if (period == 0 && run_if == nullptr && fast16 && conv_cl16_ok(cin, cout, K, precision)) {
+    if (period == 0 && run_if == nullptr && conv_cl16_ok(cin, cout, K, precision)) {
         p.tiles_per_wf = (int)((L + CT16 - 1) / CT16);
         const int64_t tiles16 = N * p.tiles_per_wf;
         if (tiles16 > 0x7fffffffLL) return STOF_ERR_UNSUPPORTED;
@@ -2130,8 +2129,7 @@ extern "C" size_t stof_train_repack_floats(int32_t cout, int32_t cin, int32_t K,
 extern "C" int stof_train_repack(const float* w, float* out, int32_t cout, int32_t cin, int32_t K, int32_t transpose_flip,
                                  int32_t precision, void* stream) {
     if (!w || !out || cout < 1 || cin < 1 || K < 1) return STOF_ERR_BAD_ARG;
-    static const bool fast16 = stof::body16_enabled();
-    if (fast16 && conv_cl16_ok(cin, cout, K, precision)) {
+    if (conv_cl16_ok(cin, cout, K, precision)) {
         // fragment image of conv_cl16_kernel (the conv entry point picks that kernel by the same test); same size
         const long long halves = (long long)K * cout * cin * 2;
         hipLaunchKernelGGL(repack_frag16_kernel, dim3(blocks_for(halves)), dim3(256), 0, static_cast<hipStream_t>(stream), w,

@@ -177,9 +177,8 @@ class TrainEngine(LayerKernels):
             raise NotImplementedError('SemiGlobalBlock sample_scale must be in [2, 256] for the gfx950 kernels')
         # split-fp16 mode, shipped geometry: conv2..conv12 + conv_last of the forward run as ONE fused sweep that also writes
         # every layer's output for the backward pass (stof_train_sweep) instead of twelve layer launches, and the backward as
-        # one sweep + one batched weight-gradient launch.  STOF_BODY16=0 changes the packed fragment order the sweeps read.
-        self.sweep = (self.prec == 1 and (not self.sgb or self.scale == 80) and self.nb == 13 and self.kb == 7
-                      and os.environ.get('STOF_BODY16', '1') != '0')
+        # one sweep + one batched weight-gradient launch.
+        self.sweep = self.prec == 1 and (not self.sgb or self.scale == 80) and self.nb == 13 and self.kb == 7
         self.sgb_sparse_taken = False       # bench.py: whether the last backward ran the sparse SemiGlobalBlock kernels
         self._bwd_overflow = None           # StofNetFunction: range-guard word of the last f16x3 backward, not yet read
 

@@ -51,23 +51,17 @@ def pack(lib, sd, r, sgs, prec=0):
     return blob.view(np.float32), desc
 
 
-def unpack_chunk(chunk, tiles, prec):
-    """Invert the fragment order documented in stofnet_amd/csrc/stof_common.h:
-    chunk [4 frags][tiles][64 lanes][16 bytes] -> dense [32*tiles rows][32 channels] (fp32 value)."""
+def unpack_chunk(chunk, tiles):
+    """Invert the fp32 fragment order documented in stofnet_amd/csrc/stof_common.h:
+    chunk [4 frags][tiles][64 lanes][4 fp32] -> dense [32*tiles rows][32 channels]."""
     raw = chunk.reshape(4, tiles, 64, 4)
     out = np.zeros((32 * tiles, 32), np.float64)
     lane = np.arange(64)
     m, hl = lane & 31, lane >> 5
     for tile in range(tiles):
-        if prec == 0:
-            for q in range(4):
-                for e in range(4):
-                    out[32 * tile + m, 8 * q + 4 * hl + e] = raw[q, tile, :, e]
-        else:
-            halves = raw.view(np.float16).reshape(4, tiles, 64, 8).astype(np.float64)
-            for ks in range(2):
-                for e in range(8):
-                    out[32 * tile + m, 16 * ks + 8 * hl + e] = halves[2 * ks, tile, :, e] + halves[2 * ks + 1, tile, :, e]
+        for q in range(4):
+            for e in range(4):
+                out[32 * tile + m, 8 * q + 4 * hl + e] = raw[q, tile, :, e]
     return out
 
 
@@ -111,8 +105,7 @@ def test_pack_layout(lib, r, sgs, prec):
         return bool(np.all(np.abs(dense - ref) <= np.maximum(2.0 ** -21 * np.abs(ref), 2.0 ** -25)))
     hdr = f[:64].view(np.uint32)
     assert hdr[0] == 0x464F5453 and int(hdr[2].view(np.int32)) == r and int(hdr[4].view(np.int32)) == prec
-    body16 = int(hdr[5]) == 1                  # header word pad0: body chunks in 16x16x32 fragment order (split-fp16, the default)
-    assert body16 == (prec == 1 and os.environ.get('STOF_BODY16', '1') != '0')
+    assert hdr[5] == (1 if prec == 1 else 0)    # header word pad0: 1 = chunks in 16x16x32 fragment order (split fp16)
     off = 64
     c1 = f[off:off + 640].reshape(64, 10); off += 640
     assert np.array_equal(c1[:, :9], sd['conv1.weight'][:, 0, :]) and np.array_equal(c1[:, 9], sd['conv1.bias'])
@@ -126,7 +119,7 @@ def test_pack_layout(lib, r, sgs, prec):
         w = sd['conv_last.weight'] if j == 12 else sd[f'conv{j + 1}.weight']
         for t in range(w.shape[2]):
             for hh in range(2):
-                dense = unpack_chunk16(chunks[c]) if body16 else unpack_chunk(chunks[c], 2, prec)
+                dense = unpack_chunk16(chunks[c]) if prec == 1 else unpack_chunk(chunks[c], 2)
                 ref = np.zeros((64, 32))
                 ref[:w.shape[0]] = w[:, 32 * hh:32 * hh + 32, t]
                 assert close(dense, ref)
@@ -150,7 +143,7 @@ def test_pack_layout(lib, r, sgs, prec):
         for ocb in range(4):
             for t in range(5):
                 for hh in range(2):
-                    dense = unpack_chunk16_sgb(cc[ocb, t, hh]) if body16 else unpack_chunk(cc[ocb, t, hh], 4, prec)
+                    dense = unpack_chunk16_sgb(cc[ocb, t, hh]) if prec == 1 else unpack_chunk(cc[ocb, t, hh], 4)
                     ref = wc[128 * ocb:128 * ocb + 128, 32 * hh:32 * hh + 32, t]
                     assert close(dense, ref)
         we = sd['semi_global_block.expand_conv.weight']                      # (64, 512, 5)
