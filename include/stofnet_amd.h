@@ -349,6 +349,41 @@ size_t stof_sincnet_workspace_bytes(const stof_sincnet_desc* desc, int64_t N, in
 int stof_sincnet_forward(const stof_sincnet_desc* desc, const float* x, int64_t N, int64_t L, const void* packed,
                          float* y, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * EDSR_1D and ESPCN_1D (models/edsr_1d.py, models/espcn_1d.py), the baselines riding on SampleShuffle1D, inference
+ * in exact fp32.  Rows of any length L >= 1.  Conventions as for stof_zonzini_*: host-only packers, the packed blob
+ * is copied to the device by the caller, no allocation and no host sync, argument checks before any HIP call (NULL
+ * pointers, N <= 0, L <= 0 or a bad desc -> STOF_ERR_BAD_ARG, workspace too small -> STOF_ERR_WORKSPACE,
+ * N (L + 1) >= 2^31 - 64 -> STOF_ERR_UNSUPPORTED).
+ * ------------------------------------------------------------------------- */
+typedef struct stof_edsr_desc {
+    int32_t num_blocks;          /* residual blocks, 0 .. 1024 (num_features is 64, num_channels is 1)                */
+    int32_t upscale_factor;      /* r in {1, 2, 4, 8, 16, 32, 64}: 64 / r channels survive the shuffle                */
+} stof_edsr_desc;
+/* params = 2 (2 B + 3) host pointers in state_dict order: conv_input.weight (64,1,3), .bias, then per block
+ * conv1.weight (64,64,3), conv1.bias, conv2.weight, conv2.bias, then conv_mid.weight, .bias, conv_output.weight
+ * (1,64/r,3), .bias.  stof_edsr_packed_bytes returns 0 for a bad desc.                                               */
+size_t stof_edsr_packed_bytes(const stof_edsr_desc* desc);
+int stof_edsr_pack_weights(const stof_edsr_desc* desc, const float* const* params, void* out, size_t out_bytes);
+/* Three channel-last buffers of (N (L + 1) + 1) x 64 floats (0 for a bad desc, N <= 0 or L <= 0).                    */
+size_t stof_edsr_workspace_bytes(const stof_edsr_desc* desc, int64_t N, int64_t L);
+/* x[N, 1, L] -> y[N, 1, L r]; trunk (optional, NULL = not written) [N, L, 64] = conv_mid + the long skip, the input
+ * of the shuffle in channel-last order.  Launches 4 + 2 B kernels on `stream`.                                       */
+int stof_edsr_forward(const stof_edsr_desc* desc, const float* x, int64_t N, int64_t L, const void* packed, float* y,
+                      float* trunk, void* workspace, size_t workspace_bytes, void* stream);
+
+typedef struct stof_espcn_desc {
+    int32_t upscale_factor;      /* r in 1 .. 64                                                                      */
+    int32_t reserved;            /* 0                                                                                 */
+} stof_espcn_desc;
+/* params = 6 host pointers: conv1.weight (64,1,5), .bias, conv2.weight (32,64,3), .bias, conv3.weight (r,32,3), .bias */
+size_t stof_espcn_packed_bytes(const stof_espcn_desc* desc);
+int stof_espcn_pack_weights(const stof_espcn_desc* desc, const float* const* params, void* out, size_t out_bytes);
+/* x[N, 1, L] -> y[N, 1, L r] = sigmoid(logits); logits (optional, NULL = not written) [N, 1, L r] = the shuffled
+ * conv3 output.  One kernel on `stream`, no workspace.                                                               */
+int stof_espcn_forward(const stof_espcn_desc* desc, const float* x, int64_t N, int64_t L, const void* packed, float* y,
+                       float* logits, void* stream);
+
 /* toa_rmse (utils/metrics.py:9-41): gt[N, G], es[N, E] fp32 with 0/NaN/inf as padding ->
  * out[N, 7] = (rmse, precision, recall, jaccard, tp, fp, fn).                  */
 int stof_toa_rmse(const float* gt, const float* es, int64_t N, int64_t G, int64_t E, float tol,

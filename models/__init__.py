@@ -1,7 +1,8 @@
 """Drop-in for the reference's `models` package (models/__init__.py): `from models import StofNet, ..., GradPeak`
 (main.py:18) resolves unchanged.  StofNet, GradPeak and the Zonzini baselines (ZonziniNetSmall / ZonziniNetLarge,
-inference only) run on the gfx950 kernels (stofnet_amd); EDSR_1D and ESPCN_1D ride on the SampleShuffle1D kernel
-(their convolutions stay stock ATen, as in the reference); SincNet runs on the gfx950 kernels for the option dict of
+inference only) run on the gfx950 kernels (stofnet_amd); EDSR_1D(1, 64, B, r | 64) and ESPCN_1D(r <= 64) run inference
+on the gfx950 kernels of csrc/riders.hip and keep the stock ATen route with the SampleShuffle1D kernel for training and
+for other widths (stofnet_amd/baselines.py); SincNet runs on the gfx950 kernels for the option dict of
 main.py (inference only; SincNet() without options raises NotImplementedError); the other comparison networks of the
 paper's table (Kuleshov, WaveUnet) are outside the accelerated path and raise when constructed."""
 from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, SincNet, StofNet, ZonziniNetLarge, ZonziniNetSmall  # noqa: F401

@@ -46,6 +46,14 @@ class SincNetDesc(ctypes.Structure):
                 ('reserved', ctypes.c_int32)]
 
 
+class EdsrDesc(ctypes.Structure):
+    _fields_ = [('num_blocks', ctypes.c_int32), ('upscale_factor', ctypes.c_int32)]
+
+
+class EspcnDesc(ctypes.Structure):
+    _fields_ = [('upscale_factor', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 class StofnetLibraryMissing(ImportError):
     pass
 
@@ -128,6 +136,15 @@ _SIGNATURES = {
     'stof_sincnet_workspace_bytes': (_c.c_size_t, [_c.POINTER(SincNetDesc), _c.c_int64, _c.c_int64]),
     'stof_sincnet_forward': (_c.c_int, [_c.POINTER(SincNetDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
                                         _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_edsr_packed_bytes': (_c.c_size_t, [_c.POINTER(EdsrDesc)]),
+    'stof_edsr_pack_weights': (_c.c_int, [_c.POINTER(EdsrDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
+    'stof_edsr_workspace_bytes': (_c.c_size_t, [_c.POINTER(EdsrDesc), _c.c_int64, _c.c_int64]),
+    'stof_edsr_forward': (_c.c_int, [_c.POINTER(EdsrDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                     _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_espcn_packed_bytes': (_c.c_size_t, [_c.POINTER(EspcnDesc)]),
+    'stof_espcn_pack_weights': (_c.c_int, [_c.POINTER(EspcnDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
+    'stof_espcn_forward': (_c.c_int, [_c.POINTER(EspcnDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                      _c.c_void_p, _c.c_void_p]),
     'stof_iq2rf': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _c.c_double,
                               _c.c_int32, _c.c_void_p]),
     'stof_toa_rmse': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_float,

@@ -1,15 +1,110 @@
 """EDSR_1D and ESPCN_1D, the two comparison networks of the reference that ride on SampleShuffle1D
 (models/edsr_1d.py:8-45, models/espcn_1d.py:8-36; selected by main.py:139-142).
 
-Their convolutions are stock ATen calls in the reference and stay stock ATen (MIOpen on ROCm) here -- they are not on
-the accelerated StofNet path ("baselines riding on the new shuffle"); the sub-pixel
-step is the gfx950 SampleShuffle1D kernel, with the inverse permutation as its backward so that the networks train.
-Constructor arguments, parameter names (checkpoints load with strict=True) and initialisation follow the reference."""
+Constructor arguments, module tree, parameter names (checkpoints load with strict=True) and initialisation follow the
+reference.  Each network has two routes:
+
+  forward_aten(x)     the reference's forward on stock ATen layers (MIOpen on ROCm) with the gfx950 SampleShuffle1D
+                      kernel (the inverse permutation as its backward), so that the networks train;
+  forward_kernels(x)  inference on the gfx950 kernels of csrc/riders.hip in exact fp32: one implicit-GEMM kernel per
+                      64 -> 64 convolution with bias, ReLU and residual in its epilogue and a fused shuffle + output conv
+                      for EDSR_1D(1, 64, B, r | 64); the whole network in one launch for ESPCN_1D(r <= 64).
+
+`forward` takes the kernels when `kernels_supported(x)` holds and no autograd graph would be recorded (under
+torch.no_grad(), or when neither x nor any parameter requires grad); everything else (CPU tensors, other dtypes,
+other widths, training) stays on `forward_aten`.  Packed weights are cached per (device, storage, `_version`) of every
+parameter, so parameter edits are picked up on their own; rows are bitwise independent of their batch, so EDSR's
+chunking under `max_workspace_bytes` does not show in the result."""
+import ctypes
+
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib
 from .sample_shuffle import SampleShuffle1D
+
+
+class _KernelRoute:
+    """Shared by EDSR_1D and ESPCN_1D: route decision, error contract and the packed-weight cache of the HIP route."""
+
+    def _kernel_params(self):
+        return list(self.parameters())
+
+    def _config_supported(self):
+        raise NotImplementedError
+
+    def kernels_supported(self, x):
+        """True when `forward_kernels(x)` can run: x float32 [N, 1, L] on the ROCm device, every parameter float32 on
+        that device, and a configuration the kernels are built for."""
+        if not (isinstance(x, torch.Tensor) and x.device.type == 'cuda' and x.dtype == torch.float32 and x.dim() == 3
+                and x.shape[1] == 1 and self._config_supported()):
+            return False
+        return all(p.dtype == torch.float32 and p.device == x.device for p in self._kernel_params())
+
+    def _takes_kernels(self, x):
+        if not self.kernels_supported(x):
+            return False
+        return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._kernel_params())))
+
+    def _check_kernels(self, x):
+        name = type(self).__name__
+        _lib.require_device(x, 'x')
+        if x.dtype != torch.float32:
+            raise TypeError(f'{name}: x must be float32 (got {x.dtype}); the gfx950 kernels are fp32 only')
+        for p in self._kernel_params():
+            if p.dtype != torch.float32:
+                raise TypeError(f'{name}: parameters must be float32 (got {p.dtype}); the gfx950 kernels are fp32 only')
+            _lib.require_device(p, 'parameter')
+        if not self.kernels_supported(x):
+            raise RuntimeError(f'{name}: the gfx950 kernels need x of shape [N, 1, L] on the parameters\' device and '
+                               f'{self._KERNEL_CONFIG} (got x {list(x.shape)}); use forward_aten')
+
+    def invalidate_packed(self):
+        """Drop the packed weights (they are rebuilt on the next forward; parameter edits are also detected on their own)."""
+        self._packed = None
+        self._packed_key = None
+
+    def packed_weights(self, device):
+        params = self._kernel_params()
+        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
+        if getattr(self, '_packed', None) is None or self._packed_key != key:
+            host = [np.ascontiguousarray(p.detach().cpu().numpy(), dtype=np.float32) for p in params]
+            self._packed = self._pack(host).to(device)
+            self._packed_key = key
+        return self._packed
+
+
+def _pack(packed_bytes, pack_weights, desc, arrs, what):
+    n = int(packed_bytes(ctypes.byref(desc)))
+    if n == 0:
+        raise ValueError(f'{what}: unsupported configuration')
+    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in arrs]
+    ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    blob = torch.zeros(n, dtype=torch.uint8)
+    _lib.check(pack_weights(ctypes.byref(desc), ptrs, ctypes.c_void_p(blob.data_ptr()), n), what)
+    return blob
+
+
+def pack_edsr_weights(num_blocks, upscale_factor, params):
+    """Host-side packing (stof_edsr_pack_weights) of the state_dict's float32 arrays in module order -> uint8 CPU blob."""
+    params = list(params)
+    if len(params) != 2 * (2 * int(num_blocks) + 3):
+        raise ValueError(f'EDSR_1D with {num_blocks} blocks has {2 * (2 * int(num_blocks) + 3)} parameters, got {len(params)}')
+    lib = _lib.lib()
+    return _pack(lib.stof_edsr_packed_bytes, lib.stof_edsr_pack_weights, _lib.EdsrDesc(int(num_blocks), int(upscale_factor)),
+                 params, 'stof_edsr_pack_weights')
+
+
+def pack_espcn_weights(upscale_factor, params):
+    """Host-side packing (stof_espcn_pack_weights) of the six state_dict arrays -> uint8 CPU blob."""
+    params = list(params)
+    if len(params) != 6:
+        raise ValueError(f'ESPCN_1D has 6 parameters, got {len(params)}')
+    lib = _lib.lib()
+    return _pack(lib.stof_espcn_packed_bytes, lib.stof_espcn_pack_weights, _lib.EspcnDesc(int(upscale_factor), 0), params,
+                 'stof_espcn_pack_weights')
 
 
 class ResidualBlock(nn.Module):
@@ -25,9 +120,11 @@ class ResidualBlock(nn.Module):
         return self.conv2(self.relu(self.conv1(x))) + x
 
 
-class EDSR_1D(nn.Module):
+class EDSR_1D(_KernelRoute, nn.Module):
     """models/edsr_1d.py:22-45: input conv + ReLU, `num_blocks` residual blocks, mid conv with the long skip,
     SampleShuffle1D (C = num_features / upscale_factor channels survive), output conv."""
+    max_workspace_bytes = 512 << 20
+    _KERNEL_CONFIG = 'num_channels = 1, num_features = 64 and an upscale_factor that divides 64'
 
     def __init__(self, num_channels=1, num_features=64, num_blocks=8, upscale_factor=4):
         super().__init__()
@@ -37,8 +134,55 @@ class EDSR_1D(nn.Module):
         self.conv_mid = nn.Conv1d(num_features, num_features, kernel_size=3, stride=1, padding=1)
         self.upscale = SampleShuffle1D(upscale_factor)
         self.conv_output = nn.Conv1d(num_features // upscale_factor, num_channels, kernel_size=3, stride=1, padding=1)
+        self._packed = None
+        self._packed_key = None
+
+    def _config_supported(self):
+        r = self.upscale.upsample_factor
+        return (self.conv_input.in_channels == 1 and self.conv_input.out_channels == 64 and isinstance(r, int)
+                and 1 <= r <= 64 and 64 % r == 0)
+
+    def _pack(self, host):
+        return pack_edsr_weights(len(self.residual_blocks), self.upscale.upsample_factor, host)
 
     def forward(self, x):
+        return self.forward_kernels(x) if self._takes_kernels(x) else self.forward_aten(x)
+
+    def forward_kernels(self, x):
+        """y [N, 1, L r] float32 on the gfx950 kernels (no autograd graph); raises where they do not apply."""
+        return self._run(x, False)[0]
+
+    def forward_with_trunk(self, x):
+        """(y [N, 1, L r], the input of `upscale` [N, 64, L] = conv_mid + the long skip), on the gfx950 kernels."""
+        y, trunk = self._run(x, True)
+        return y, trunk.transpose(1, 2)
+
+    def _run(self, x, want_trunk):
+        self._check_kernels(x)
+        N, L, r = int(x.shape[0]), int(x.shape[-1]), int(self.upscale.upsample_factor)
+        y = torch.empty((N, 1, L * r), dtype=torch.float32, device=x.device)
+        trunk = torch.empty((N, L, 64), dtype=torch.float32, device=x.device) if want_trunk else None
+        if N == 0 or L == 0:
+            return y, trunk
+        x = x.detach().contiguous()
+        packed = self.packed_weights(x.device)
+        lib = _lib.lib()
+        desc = _lib.EdsrDesc(len(self.residual_blocks), r)
+        per_row = int(lib.stof_edsr_workspace_bytes(ctypes.byref(desc), 1, L))
+        chunk = max(1, min(N, int(self.max_workspace_bytes) // per_row))
+        ws_bytes = int(lib.stof_edsr_workspace_bytes(ctypes.byref(desc), chunk, L))
+        with torch.cuda.device(x.device):
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+            stream = _lib.stream_ptr(x.device)
+            for r0 in range(0, N, chunk):
+                n = min(chunk, N - r0)
+                _lib.check(lib.stof_edsr_forward(
+                    ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), n, L, _lib.ptr(packed),
+                    ctypes.c_void_p(y[r0].data_ptr()), None if trunk is None else ctypes.c_void_p(trunk[r0].data_ptr()),
+                    _lib.ptr(ws), ws_bytes, stream), 'stof_edsr_forward')
+        return y, trunk
+
+    def forward_aten(self, x):
         first = self.relu(self.conv_input(x))
         out = first
         for block in self.residual_blocks:
@@ -47,9 +191,10 @@ class EDSR_1D(nn.Module):
         return self.conv_output(self.upscale(out))
 
 
-class ESPCN_1D(nn.Module):
+class ESPCN_1D(_KernelRoute, nn.Module):
     """models/espcn_1d.py:8-36: conv5 - tanh - conv3 - tanh - conv3 - SampleShuffle1D - sigmoid, with the reference's
     normal initialisation (std 0.001 for the layer fed by 32 channels, He-style otherwise, zero biases)."""
+    _KERNEL_CONFIG = 'an upscale_factor of at most 64'
 
     def __init__(self, upscale_factor):
         super().__init__()
@@ -62,8 +207,43 @@ class ESPCN_1D(nn.Module):
                 std = 0.001 if m.in_channels == 32 else (2.0 / (m.out_channels * m.weight[0][0].numel())) ** 0.5
                 nn.init.normal_(m.weight.data, 0.0, std)
                 nn.init.zeros_(m.bias.data)
+        self._packed = None
+        self._packed_key = None
+
+    def _config_supported(self):
+        r = self.sample_shuffle.upsample_factor
+        return isinstance(r, int) and 1 <= r <= 64
+
+    def _pack(self, host):
+        return pack_espcn_weights(self.sample_shuffle.upsample_factor, host)
 
     def forward(self, x):
+        return self.forward_kernels(x) if self._takes_kernels(x) else self.forward_aten(x)
+
+    def forward_kernels(self, x):
+        """y [N, 1, L r] float32 on the gfx950 kernel (no autograd graph); raises where it does not apply."""
+        return self._run(x, False)[0]
+
+    def forward_with_logits(self, x):
+        """(y [N, 1, L r], the output of `sample_shuffle` [N, 1, L r], i.e. the map before the sigmoid)."""
+        return self._run(x, True)
+
+    def _run(self, x, want_logits):
+        self._check_kernels(x)
+        N, L, r = int(x.shape[0]), int(x.shape[-1]), int(self.sample_shuffle.upsample_factor)
+        y = torch.empty((N, 1, L * r), dtype=torch.float32, device=x.device)
+        logits = torch.empty_like(y) if want_logits else None
+        if N == 0 or L == 0:
+            return y, logits
+        x = x.detach().contiguous()
+        packed = self.packed_weights(x.device)
+        desc = _lib.EspcnDesc(r, 0)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().stof_espcn_forward(ctypes.byref(desc), _lib.ptr(x), N, L, _lib.ptr(packed), _lib.ptr(y),
+                                                     _lib.ptr(logits), _lib.stream_ptr(x.device)), 'stof_espcn_forward')
+        return y, logits
+
+    def forward_aten(self, x):
         x = torch.tanh(self.conv1(x))
         x = torch.tanh(self.conv2(x))
         return torch.sigmoid(self.sample_shuffle(self.conv3(x)))
