@@ -2,7 +2,8 @@
 //
 //   sgb_contract_pool : x -> relu(conv1) -> contract_conv 64->512 k5 (MFMA) -> lrelu
 //                       -> max-pool 80  => pooled[N][P][512]        (models/stofnet.py:45,100-103)
-//   expand (train.hip conv_cl_kernel, stream mode): pooled -> expand_conv 512->64 k5 -> lrelu => sgb[N][P][64] (:106-107)
+//   sgb_expand (sgb_expand.hip; exact fp32: train.hip conv_cl_kernel, stream mode):
+//                       pooled -> expand_conv 512->64 k5 -> lrelu => sgb[N][P][64]      (:106-107)
 //   body_sweep        : x, sgb -> relu(conv1) + upsample/pad(sgb) (:45,108-115) -> conv2..conv12
 //                       with the residual pattern of :51-62 -> conv_last -> SampleShuffle1D store
 //                       (:65, utils/sample_shuffle.py:10-28)        => y[N][L*r]
@@ -27,9 +28,13 @@
 #include "stof_common.h"
 #include "stof_hip_util.h"
 
-// expand_conv 512->64 k5 on the pooled grid + lrelu runs on the channel-last MFMA conv of train.hip in stream mode (the P
-// pooled columns of every waveform followed by 2 zero gap rows form one long row sequence, so the 128-row tiles are full).
+// expand_conv 512->64 k5 on the pooled grid + lrelu: the P pooled columns of every waveform followed by 2 zero gap rows form
+// one long row sequence, so the row tiles are full.  Split fp16 has a kernel of its own (sgb_expand.hip: same arithmetic as
+// the channel-last MFMA conv of train.hip, a block's five weight taps staged at once); exact fp32 runs on that conv in
+// stream mode.
 namespace stof {
+int launch_sgb_expand(const float* pooled, const float* w, const float* bias, float* sgb, int64_t nb, int64_t P,
+                      hipStream_t stream, const int* run_if);
 int launch_conv_cl(const float* x, const float* w, const float* bias, const float* residual, const float* saved, float* y,
                    int64_t N, int64_t L, int32_t cin, int32_t cout, int32_t K, int32_t act, int32_t precision,
                    int32_t period, int32_t valid_len, hipStream_t stream, const int* run_if);
@@ -1137,8 +1142,17 @@ constexpr int BODY_P2_C1F = 640;        // conv1 taps + bias [64][10] kept in LD
 
 // ----------------------------------------------------------------------------------
 // SemiGlobalBlock contracting path: relu(conv1) -> conv 64->512 k5 -> lrelu -> maxpool 80
-// One work-group = NW pooling windows of one waveform.  Time sits on the MFMA M axis so
-// the pool is an in-lane max over accumulator registers plus one cross-half shuffle.
+// One work-group = NW consecutive entries of the flat stream of N * P pooling windows (flat index g = n * P + w), so no
+// tile multiplies out a window that does not exist when P is odd; only the last tile of a launch can hold an absent
+// window (g >= N * P), which loads nothing and stores nothing.  The windows of a tile may belong to different waveforms:
+// each has its own WR = 84 conv1 rows (80 + the k5 halo) and 92 raw samples in LDS, zero outside [0, L) of its own
+// waveform.  Time sits on the MFMA M axis so the pool is an in-lane max over accumulator registers plus one cross-half
+// shuffle.  LDS banks: a window's rows start at a multiple of the row stride (84 rows of 288 B, or of 272 B in fp32), and
+// that base is the same for every lane of one ds_read_b128 in the split-fp16 form (a unit reads one window), so the
+// conflict-freedom of the 288-byte stride (BodyLds) carries over unchanged.  In the fp32 form (272-byte rows, lane = row)
+// the one 32-row M-tile in five that straddles output row 80 adds 4 rows for lanes 16..31 of each half-wave; in the
+// hardware's lane groups {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} the shifted rows then meet four unshifted ones on the
+// same banks (2-way, one more LDS cycle per group).  That read feeds four 64-cycle fp32 MFMAs, so it stays hidden.
 // ----------------------------------------------------------------------------------
 struct SgbParams {
     const float* x;        // [N][L]
@@ -1146,7 +1160,7 @@ struct SgbParams {
     const float* c1;       // [64][10]
     const float* cbias;    // [512]
     const float* chunks;   // [SGB_NCHUNK][SGB_CHUNK_F]
-    int N, L, P, tiles_per_wf;
+    int N, L, P;
     const int* run_if;     // as BodyParams::run_if
     unsigned char* arg;    // training (ARG): [N][P][512] row offset (0..79) of the window's FIRST maximum, for the pool's backward
 };
@@ -1158,8 +1172,10 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
     static_assert(NW % 2 == 0, "80*NW must be a multiple of 32");
     constexpr int ROWS = SGB_SCALE * NW;          // output rows of the tile
     constexpr int MT = ROWS / 32;
-    constexpr int TR = ROWS + 4;                  // conv1 rows needed (k5: +-2)
-    constexpr int RAWN = TR + 8;                  // raw samples needed (k9: +-4)
+    constexpr int WR = SGB_SCALE + 4;             // conv1 rows of one window (k5: +-2)
+    constexpr int WRAW = WR + 8;                  // raw samples of one window (k9: +-4)
+    constexpr int TR = NW * WR;
+    constexpr int RAWN = NW * WRAW;
     constexpr int RF = SHAPE == 16 ? ROWF16 : ROWF;           // 288-byte rows for the 16x16x32 operand reads (see BodyLds)
     constexpr int ROWB = RF * 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1169,11 +1185,17 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int ln = lane & 31, lh = lane >> 5;
-    const int n = blockIdx.x / p.tiles_per_wf;
-    const int w0 = (blockIdx.x - n * p.tiles_per_wf) * NW;
     const int L = p.L;
-    const int tbase = SGB_SCALE * w0 - 2;         // time of act row 0
+    const int g0 = blockIdx.x * NW;               // flat index of the tile's first window
+    const int gtot = p.N * p.P;
     if (p.run_if != nullptr && *p.run_if == 0) return;
+    // window wi of the tile: waveform, time of its act row 0, present
+    auto window = [&](int wi, int& n, int& tbase) -> bool {
+        const int g = g0 + wi;
+        n = g / p.P;
+        tbase = SGB_SCALE * (g - n * p.P) - 2;
+        return g < gtot;
+    };
 
     const uint4* const wbase = reinterpret_cast<const uint4*>(p.chunks) + wave * 64 + lane;
     auto wload = [&](int c, int f) -> uint4 { return wbase[((size_t)c * FRAGS_PER_CHUNK + f) * 256]; };
@@ -1185,8 +1207,11 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
     }
 
     for (int i = tid; i < RAWN; i += 256) {
-        const int t = tbase - 4 + i;
-        raw[i] = (t >= 0 && t < L) ? p.x[(size_t)n * L + t] : 0.f;
+        const int wi = i / WRAW;
+        int n, tbase;
+        const bool present = window(wi, n, tbase);
+        const int t = tbase - 4 + (i - wi * WRAW);
+        raw[i] = (present && t >= 0 && t < L) ? p.x[(size_t)n * L + t] : 0.f;
     }
     __syncthreads();
     {   // relu(conv1) rows of the tile, zero outside [0, L)
@@ -1199,16 +1224,20 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
             b1[i] = p.c1[(4 * cq + i) * 10 + 9];
         }
         for (int row = rl; row < TR; row += 16) {
-            const int t = tbase + row;
+            const int wi = row / WR;
+            int n, tbase;
+            const bool present = window(wi, n, tbase);
+            const int t = tbase + (row - wi * WR);
+            const float* const rw = raw + row + 8 * wi;          // = raw + wi * WRAW + (row - wi * WR)
             float v[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float a = b1[i];
 #pragma unroll
-                for (int d = 0; d < 9; ++d) a = fmaf(w1[i][d], raw[row + d], a);
+                for (int d = 0; d < 9; ++d) a = fmaf(w1[i][d], rw[d], a);
                 v[i] = fmaxf(a, 0.f);
             }
-            const bool valid = (t >= 0) && (t < L);
+            const bool valid = present && (t >= 0) && (t < L);
             store_act4<PREC>(act + row * ROWB, 4 * cq,
                              valid ? make_float4(v[0], v[1], v[2], v[3]) : make_float4(0.f, 0.f, 0.f, 0.f));
         }
@@ -1238,7 +1267,7 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
             auto aload = [&](uint4 (&a)[MW][2], int uu) {
                 const int cc = uu / NW, w = uu % NW;
                 const int d = cc >> 1, hh = cc & 1;
-                const char* arow = act + (SGB_SCALE * w + j16 + d) * ROWB + 64 * hh + 16 * q4;
+                const char* arow = act + (WR * w + j16 + d) * ROWB + 64 * hh + 16 * q4;
 #pragma unroll
                 for (int m = 0; m < MW; ++m) {
                     a[m][0] = ldq(arow + 16 * m * ROWB);
@@ -1315,7 +1344,7 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
                             mval = take ? ov : mval;
                             bi = take ? oi : bi;
                         }
-                        if (q4 == 0 && w0 + w < p.P) p.arg[((size_t)n * p.P + w0 + w) * NF_SGB + oc] = (unsigned char)bi;
+                        if (q4 == 0 && g0 + w < gtot) p.arg[(size_t)(g0 + w) * NF_SGB + oc] = (unsigned char)bi;
                     } else {
 #pragma unroll
                         for (int m = 0; m < MW; ++m)
@@ -1326,13 +1355,20 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
                     }
                     mval += bias;
                     mval = mval > 0.f ? mval : 0.01f * mval;
-                    if (q4 == 0 && w0 + w < p.P)
-                        p.pooled[((size_t)n * p.P + w0 + w) * NF_SGB + oc] = mval;
+                    if (q4 == 0 && g0 + w < gtot)
+                        p.pooled[(size_t)(g0 + w) * NF_SGB + oc] = mval;
                 }
             }
         }
     } else {
-    // ---- exact fp32 on v_mfma_f32_32x32x2_f32
+    // ---- exact fp32 on v_mfma_f32_32x32x2_f32.  The 32-row M-tiles run over the tile's 80 NW output rows and straddle
+    // the window boundaries: output row r reads activation row r + 4 (r / 80).
+    int arow_off[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const int r = 32 * m + ln;
+        arow_off[m] = (r + 4 * (r / SGB_SCALE)) * ROWB;
+    }
     for (int ocb = 0; ocb < 4; ++ocb) {
         floatx16 acc[MT];
 #pragma unroll
@@ -1347,9 +1383,9 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
         auto aload = [&](uint4 (&a)[MT], int uu) {
             const int cc = uu / UPC, sub = uu % UPC;
             const int d = cc >> 1, hh = cc & 1;
-            const char* arow = act + (ln + d) * ROWB;
+            const char* arow = act + d * ROWB + act_frag_off(sub, hh, lh);
 #pragma unroll
-            for (int m = 0; m < MT; ++m) a[m] = ldq(arow + 32 * m * ROWB + act_frag_off(sub, hh, lh));
+            for (int m = 0; m < MT; ++m) a[m] = ldq(arow + arow_off[m]);
         };
         auto do_unit = [&](uint4 (&acur)[MT], uint4 (&anext)[MT], int uu) {
             const int cc = uu / UPC, sub = uu % UPC;
@@ -1393,8 +1429,8 @@ __global__ __launch_bounds__(256, SGB_WAVES_PER_SIMD) void sgb_contract_pool_ker
             float mval = fmaxf(wmax[w], __shfl_xor(wmax[w], 32));
             mval += bias;
             mval = mval > 0.f ? mval : 0.01f * mval;
-            if (lh == 0 && w0 + w < p.P)
-                p.pooled[((size_t)n * p.P + w0 + w) * NF_SGB + oc] = mval;
+            if (lh == 0 && g0 + w < gtot)
+                p.pooled[(size_t)(g0 + w) * NF_SGB + oc] = mval;
         }
     }
     }   // fp32
@@ -1463,7 +1499,7 @@ struct OnsetArgs {                        // non-null ws: stof_forward_onsets
 constexpr int64_t SUB_BATCH = 4096;      // rows whose SGB maps share one workspace
 
 constexpr size_t sgb_lds_bytes(int rowf) {
-    return (size_t)((SGB_SCALE * SGB_NW + 4) * rowf + SGB_SCALE * SGB_NW + 12) * sizeof(float);
+    return (size_t)SGB_NW * ((SGB_SCALE + 4) * rowf + SGB_SCALE + 12) * sizeof(float);    // per window: 84 rows + 92 raw samples
 }
 
 template <int PREC>
@@ -1520,14 +1556,17 @@ int launch_forward(const stof_net_desc* desc, const void* packed_dev, const floa
             SgbParams sp;
             sp.x = xb; sp.pooled = pooled; sp.c1 = c1; sp.cbias = cbias; sp.chunks = cchunks;
             sp.N = (int)nb; sp.L = (int)L; sp.P = (int)P;
-            sp.tiles_per_wf = (int)((P + SGB_NW - 1) / SGB_NW);
             sp.run_if = run_if;
             sp.arg = nullptr;
-            hipLaunchKernelGGL(sgb_kernel, dim3((unsigned)(nb * sp.tiles_per_wf)), dim3(256), sgb_bytes, stream, sp);
+            hipLaunchKernelGGL(sgb_kernel, dim3((unsigned)((nb * P + SGB_NW - 1) / SGB_NW)), dim3(256), sgb_bytes, stream, sp);
             if (ev) (void)hipEventRecord(static_cast<hipEvent_t>(events[1]), stream);
             {
-                const int st = stof::launch_conv_cl(pooled, ew, ebias, nullptr, nullptr, sgb, 1, nb * (P + 2), NF_SGB, NF, 5,
-                                                    /*act = leaky ReLU*/ 2, PREC, (int)(P + 2), (int)P, stream, run_if);
+                int st;
+                if constexpr (PREC == STOF_PREC_F16X3)
+                    st = stof::launch_sgb_expand(pooled, ew, ebias, sgb, nb, P, stream, run_if);
+                else
+                    st = stof::launch_conv_cl(pooled, ew, ebias, nullptr, nullptr, sgb, 1, nb * (P + 2), NF_SGB, NF, 5,
+                                              /*act = leaky ReLU*/ 2, PREC, (int)(P + 2), (int)P, stream, run_if);
                 if (st != STOF_OK) return st;
             }
             if (ev) (void)hipEventRecord(static_cast<hipEvent_t>(events[2]), stream);
@@ -1945,10 +1984,9 @@ extern "C" int stof_train_sgb_contract_pool(const float* conv1_w, const float* c
     SgbParams sp;
     sp.x = x; sp.pooled = pooled; sp.c1 = a.blob; sp.cbias = a.blob + 640; sp.chunks = a.blob + 640 + NF_SGB;
     sp.N = (int)N; sp.L = (int)L; sp.P = (int)P;
-    sp.tiles_per_wf = (int)((P + SGB_NW - 1) / SGB_NW);
     sp.run_if = nullptr; sp.arg = arg;
-    if (N * sp.tiles_per_wf > 0x7fffffffLL) return STOF_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(N * sp.tiles_per_wf)), dim3(256), sgb_lds_bytes(ROWF16), stream, sp);
+    if (N * P + SGB_NW > 0x7fffffffLL) return STOF_ERR_UNSUPPORTED;             // flat window indices are int32
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((N * P + SGB_NW - 1) / SGB_NW)), dim3(256), sgb_lds_bytes(ROWF16), stream, sp);
     return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP;
 }
 
