@@ -288,6 +288,45 @@ int stof_grad_peak_detect_f64(const double* env, int64_t N, int64_t L, int32_t g
 int stof_iq2rf(const float* iq, float* rf, int64_t N, int64_t len, double rescale_factor,
                double fc, double fs, int32_t normalize, void* stream);
 
+/* Training augmentation (utils/transforms.py: NormalizeVol -> CropChannelData -> AddNoise, chained per sample at
+ * main.py:49,54,82) for a batch of rows in one launch.  Per row, in this order:
+ *   normalize   x / max|x| over the whole row.
+ *   crop        when 0 < crop_ratio < 1 (else the row passes through, start = 0, gt_out = gt):
+ *                 width = rint(L * crop_ratio), ref = rint(gt[row, 0]) (half to even; a NaN gt counts as 0),
+ *                 start = max(0, ref - width/2), end = min(ref + width/2, L); end == L -> start = end - width;
+ *                 start == 0 -> end = width; max_dist = min(ref - start, end - ref);
+ *                 shift uniform on the integers [-min(start, max_dist/2), min(L - end, max_dist/2)) (floor divisions),
+ *                 0 where that range is empty (the reference's randint raises there);
+ *                 y[j] = x[start + shift + j] for j < width, 0 beyond; gt_out[row, 0] = gt[row, 0] - (start + shift);
+ *                 columns c >= 1 move alike and become 0 (the "no echo" value of main.py:217) when they were <= 0 or NaN
+ *                 or land outside [0, width); start[row] = start + shift.
+ *   noise       U[j] uniform on [0, 1) for all L samples of the padded row; n = 2 (U - 0.5) when the cropped row has a
+ *               negative sample, else U; y += n * sqrt(10^(-snr_db/10) * sum y^2 / sum n^2).  The sums are double
+ *               accumulators combined in a fixed tree: bitwise the same from run to run.
+ * Generator: Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (j >> 2, row, call, (rank << 1) | stream_id);
+ * word j & 3 gives U = (word >> 8) * 2^-24.  Stream 0 is the noise.  Stream 1 is the crop shift: with w = word 0 of block 0,
+ * shift = low + (((w >> 8) * (high - low)) >> 24) on [low, high).  A draw depends on its coordinates only.
+ * Overrides: noise[N, L] (uniforms used instead of stream 0) and shift[N] (used instead of the drawn shift; start + shift
+ * is clamped into [0, L - width]); either may be NULL.
+ * x[N, L], gt[N, G] (NULL with G = 0; a crop needs G >= 1) -> y[N, L] (y != x), gt_out[N, G], start[N].  One launch on
+ * `stream`.  NULL x / y / start / desc, negative sizes, y == x, a missing gt, rank >= 2^31 or (add_noise) a non-finite
+ * snr_db -> STOF_ERR_BAD_ARG; an odd crop width (the reference asserts on it) or N, L >= 2^31 -> STOF_ERR_UNSUPPORTED;
+ * N == 0 or L == 0 -> STOF_OK without a launch.                                                                       */
+typedef struct stof_augment_desc {
+    uint64_t seed;
+    double crop_ratio;           /* crop when 0 < crop_ratio < 1                                     */
+    double snr_db;               /* read when add_noise != 0                                         */
+    int32_t normalize;
+    int32_t add_noise;
+    uint32_t rank;               /* < 2^31                                                           */
+    uint32_t call;               /* one value per training step                                      */
+} stof_augment_desc;
+int stof_augment(const stof_augment_desc* desc, const float* x, const float* gt, int64_t N, int64_t L, int64_t G,
+                 const float* noise, const int32_t* shift, float* y, float* gt_out, int32_t* start, void* stream);
+/* out[N, L] = the uniforms stream `stream_id` (0 or 1) of the generator above hands out for (seed, rank, call). */
+int stof_augment_uniforms(uint64_t seed, uint32_t rank, uint32_t call, int32_t stream_id, float* out, int64_t N, int64_t L,
+                          void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Zonzini baselines (models/zonzini.py: ZonziniNetSmall / ZonziniNetLarge), inference in exact fp32.
  * ------------------------------------------------------------------------- */

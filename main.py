@@ -9,7 +9,10 @@ load_state_dict (main.py:173-177), the eval loop's `model(frame)` -> `mask2coord
 (main.py:199-289: Gaussian-mask loss, AdamW, CosineAnnealingLR per epoch, EarlyStopping on the
 summed validation loss, checkpoint `<run_name>_rf-scale<rf>_epoch_<e>.pth`, main.py:423-426) on the
 HIP training kernels; launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
-one flat gradient all-reduce per step over RCCL).  What it drops: datasets (absent from the reference
+one flat gradient all-reduce per step over RCCL).  `augment=True` puts the reference's training transforms in front of every
+training step (main.py:49,54,82: CropChannelData(crop_ratio) + AddNoise(snr_db) on chirp data, AddNoise alone otherwise) as
+one launch of the device kernel (stofnet_amd/augment.py); `shuffle=True` reorders the training rows every epoch
+(main.py:110).  What it drops: datasets (absent from the reference
 mount) and wandb.  Inputs come from `input_file` (.npy) or from synthetic echoes with known onsets.
 """
 import json
@@ -160,10 +163,27 @@ def main(argv=None):
     return es_all, summary
 
 
+def epoch_batches(n_rows, bs, epoch, rank, world, shuffle=False, seed=0):
+    """[(global batch index, rows of that batch)] of `rank` for one epoch.  Without `shuffle` the rows are slices in file
+    order.  With it they index a fresh permutation of the training rows (the DataLoader's shuffle of main.py:110), drawn
+    from (seed, epoch) alone and before rank_batches: every rank sees the same order and takes its own batches of it."""
+    from stofnet_amd.sharding import rank_batches
+    mine = rank_batches(n_rows // bs, rank, world)                       # the same number of steps on every rank
+    if not shuffle:
+        return [(b, slice(b * bs, (b + 1) * bs)) for b in mine]
+    order = np.random.default_rng([int(seed), int(epoch)]).permutation(n_rows)
+    return [(b, order[b * bs:(b + 1) * bs]) for b in mine]
+
+
 def train(model, frames, gt, cfg, log=None):
-    """main.py:199-289 + 403-410 + 423-426 on the HIP training kernels (stofnet_amd/training.py)."""
+    """main.py:199-289 + 403-410 + 423-426 on the HIP training kernels (stofnet_amd/training.py).
+
+    With `augment=True` every training batch goes through stofnet_amd.augment.Augment first (generator: seed = cfg.seed,
+    rank = RANK, one `call` per step) and the ground truth moves with the crop window before it becomes sample indices.
+    The held-out validation tail is NOT augmented.  This differs from the reference on purpose: there the validation split
+    shares the noisy dataset, but early stopping with delta = 1e-6 needs a loss that does not move with the noise draw."""
     import torch.distributed as dist
-    from stofnet_amd.sharding import agree_any, rank_batches
+    from stofnet_amd.sharding import agree_any
     from stofnet_amd.training import StofNetTrainer
     if gt is None:
         raise RuntimeError('training needs ground-truth onsets (synthetic echoes or a labelled input)')
@@ -178,11 +198,20 @@ def train(model, frames, gt, cfg, log=None):
     n_val = max(bs, int(frames.shape[0] * 0.1) // bs * bs)              # held-out tail for early stopping
     tr_x, tr_gt = frames[:-n_val], gt[:-n_val]
     va_x, va_gt = frames[-n_val:], gt[-n_val:]
-    mine = rank_batches(tr_x.shape[0] // bs, rank, world)                # the same number of steps on every rank
+    shuffle = bool(getattr(cfg, 'shuffle', False))
+    aug = None
+    if bool(getattr(cfg, 'augment', False)):
+        from stofnet_amd.augment import Augment
+        chirp = 'chirp' in str(cfg.data_dir).lower()                     # main.py:49,54 crop + noise | main.py:82 noise
+        aug = Augment(snr_db=float(cfg.snr_db), crop_ratio=float(cfg.crop_ratio) if chirp else None, seed=int(cfg.seed),
+                      rank=rank)
     best, bad, history = float('inf'), 0, []
 
     def gt_true_of(g):
-        g = torch.from_numpy(np.nan_to_num(g, nan=0.0)).to(cfg.device)
+        if isinstance(g, np.ndarray):
+            g = torch.from_numpy(np.nan_to_num(g, nan=0.0)).to(cfg.device)
+        else:
+            g = torch.nan_to_num(g, nan=0.0)
         g = torch.where(g <= 0, torch.zeros_like(g), g)                  # main.py:217
         return torch.round(g.unsqueeze(1) * r).long()                    # main.py:218
 
@@ -221,10 +250,13 @@ def train(model, frames, gt, cfg, log=None):
             tr.set_lr_cosine(e, int(cfg.epochs), float(cfg.lr))          # CosineAnnealingLR stepped per epoch
         model.train()
         tot = 0.0
-        for b in mine:
-            sl = slice(b * bs, (b + 1) * bs)
+        mine = epoch_batches(tr_x.shape[0], bs, e, rank, world, shuffle, int(cfg.seed))
+        for b, sl in mine:
             step = autograd_step if autograd else tr.train_step
-            loss, _ = step(torch.from_numpy(tr_x[sl]).to(cfg.device), gt_true_of(tr_gt[sl]))
+            frame, g = torch.from_numpy(tr_x[sl]).to(cfg.device), tr_gt[sl]
+            if aug is not None:
+                frame, g, _ = aug(frame, torch.from_numpy(g).to(cfg.device))
+            loss, _ = step(frame, gt_true_of(g))
             tot += float(loss)
             if log is not None and log.enabled:
                 log.log({'train_step': e * len(mine) + (b - rank) // world + 1, 'train_loss': float(loss)})      # main.py:251-255

@@ -54,6 +54,12 @@ class EspcnDesc(ctypes.Structure):
     _fields_ = [('upscale_factor', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class AugmentDesc(ctypes.Structure):
+    _fields_ = [('seed', ctypes.c_uint64), ('crop_ratio', ctypes.c_double), ('snr_db', ctypes.c_double),
+                ('normalize', ctypes.c_int32), ('add_noise', ctypes.c_int32), ('rank', ctypes.c_uint32),
+                ('call', ctypes.c_uint32)]
+
+
 class StofnetLibraryMissing(ImportError):
     pass
 
@@ -147,6 +153,10 @@ _SIGNATURES = {
                                       _c.c_void_p, _c.c_void_p]),
     'stof_iq2rf': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _c.c_double,
                               _c.c_int32, _c.c_void_p]),
+    'stof_augment': (_c.c_int, [_c.POINTER(AugmentDesc), _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p,
+                                _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_augment_uniforms': (_c.c_int, [_c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                         _c.c_void_p]),
     'stof_toa_rmse': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_float,
                                  _c.c_void_p, _c.c_void_p]),
     'stof_train_repack_floats': (_c.c_size_t, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32]),

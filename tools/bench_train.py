@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Time the training step (BASELINE.json configs[4], one GPU): fwd+bwd+AdamW at rf upsample 10, L=2000."""
+"""Time the training step (BASELINE.json configs[4], one GPU): fwd+bwd+AdamW at rf upsample 10, L=2000.
+--augment puts what main.py augment=True adds in front of every step: the augmentation launch (crop .75 + 30 dB noise,
+stofnet_amd/augment.py) and the conversion of the shifted ground truth into sample indices."""
 import argparse
 import json
 import sys
@@ -19,6 +21,7 @@ ap.add_argument('--length', type=int, default=2000)
 ap.add_argument('--r', type=int, default=10)
 ap.add_argument('--steps', type=int, default=10)
 ap.add_argument('--warmup', type=int, default=2)
+ap.add_argument('--augment', action='store_true')
 a = ap.parse_args()
 dev = torch.device('cuda:0')
 sd = synth.synth_state_dict(a.r, seed=1, semi_global_scale=80)
@@ -29,13 +32,25 @@ tr = StofNetTrainer(m)
 x = torch.from_numpy(synth.synth_echo(a.batch, a.length, seed=4)).to(dev)
 rng = np.random.default_rng(0)
 gt = torch.from_numpy(np.sort(rng.integers(1, a.length * a.r, size=(a.batch, 1, 2)), -1)).to(dev)
+if a.augment:
+    from stofnet_amd.augment import Augment
+    aug = Augment(snr_db=30., crop_ratio=.75, seed=3008)
+    gt_samples = gt[:, 0, :].float() / a.r
+
+    def one_step():
+        frame, g, _ = aug(x, gt_samples)
+        g = torch.where(g <= 0, torch.zeros_like(g), g)
+        return tr.train_step(frame, torch.round(g.unsqueeze(1) * a.r).long())
+else:
+    def one_step():
+        return tr.train_step(x, gt)
 for _ in range(a.warmup):
-    tr.train_step(x, gt)
+    one_step()
 torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
 e0.record()
 for _ in range(a.steps):
-    loss, _ = tr.train_step(x, gt)
+    loss, _ = one_step()
 e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / a.steps
@@ -43,4 +58,4 @@ ms = e0.elapsed_time(e1) / a.steps
 from oracle.stofnet_oracle import flops_per_waveform
 fl = 3 * flops_per_waveform(a.length, a.r) * a.batch
 print(json.dumps({'train_step_ms': ms, 'waveforms_per_s': a.batch / ms * 1e3, 'batch': a.batch, 'L': a.length, 'r': a.r,
-                  'tflops_fp32': fl / ms / 1e9, 'loss': float(loss)}))
+                  'tflops_fp32': fl / ms / 1e9, 'loss': float(loss), 'augment': bool(a.augment)}))
