@@ -423,6 +423,30 @@ int stof_espcn_pack_weights(const stof_espcn_desc* desc, const float* const* par
 int stof_espcn_forward(const stof_espcn_desc* desc, const float* x, int64_t N, int64_t L, const void* packed, float* y,
                        float* logits, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Wave-U-Net (models/wave_unet.py, `main.py model=unet`), inference in exact fp32 with eval-mode BatchNorm folded
+ * into the convolutions by the host packer (in double).  Served: channels_interval = 16, n_layers 1 .. 12, rows of a
+ * length L that is a multiple of 2^n_layers.  Conventions as for stof_edsr_*; anything outside the served range ->
+ * STOF_ERR_BAD_ARG (0 from the size functions), N = 0 -> STOF_OK without a launch, N L >= 2^31 - 64 ->
+ * STOF_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+typedef struct stof_waveunet_desc {
+    int32_t n_layers;            /* n in 1 .. 12                                                                      */
+    int32_t channels_interval;   /* 16                                                                                */
+} stof_waveunet_desc;
+/* params = 6 (2 n + 1) + 2 host pointers, the state dict in module order without the num_batches_tracked entries:
+ * per block (encoder.0 .. n-1, middle, decoder.0 .. n-1) conv weight, conv bias, BN weight, BN bias, running mean,
+ * running var; then out.0.weight (1,17,1) and out.0.bias.  The blob layout is documented in csrc/waveunet.hip.      */
+size_t stof_waveunet_packed_bytes(const stof_waveunet_desc* desc);
+int stof_waveunet_pack_weights(const stof_waveunet_desc* desc, const float* const* params, void* out, size_t out_bytes);
+/* The n skips [N, L / 2^i, 16 (i + 1)], the middle map and two decoder buffers [N, L, 16] (0 for a bad desc, N <= 0
+ * or a bad L).                                                                                                      */
+size_t stof_waveunet_workspace_bytes(const stof_waveunet_desc* desc, int64_t N, int64_t L);
+/* x[N, 1, L] -> y[N, 1, L]; bottleneck (optional) [N, L / 2^n, 16 n] = the middle block's output, channel-last;
+ * logits (optional) [N, 1, L] = the output convolution before the tanh.  Launches 2 n + 2 kernels on `stream`.      */
+int stof_waveunet_forward(const stof_waveunet_desc* desc, const float* x, int64_t N, int64_t L, const void* packed, float* y,
+                          float* bottleneck, float* logits, void* workspace, size_t workspace_bytes, void* stream);
+
 /* toa_rmse (utils/metrics.py:9-41): gt[N, G], es[N, E] fp32 with 0/NaN/inf as padding ->
  * out[N, 7] = (rmse, precision, recall, jaccard, tp, fp, fn).                  */
 int stof_toa_rmse(const float* gt, const float* es, int64_t N, int64_t G, int64_t E, float tol,

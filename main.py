@@ -3,7 +3,7 @@
 (reference main.py:29-34,133-177,292-347), running the MI355X-native hot path.
 
 What it keeps: config.yaml + CLI merge, seeding (main.py:39-41), the model switch
-(stofnet / edsr / espcn / zonzini / sincnet / gradpeak, main.py:133-167), checkpoint lookup by file-name prefix with strict
+(stofnet / edsr / espcn / zonzini / sincnet / unet / gradpeak, main.py:133-167), checkpoint lookup by file-name prefix with strict
 load_state_dict (main.py:173-177), the eval loop's `model(frame)` -> `mask2coords` ->
 `toa_rmse` sequence (main.py:314,320,347), and with `evaluate=False` the training loop
 (main.py:199-289: Gaussian-mask loss, AdamW, CosineAnnealingLR per epoch, EarlyStopping on the
@@ -28,7 +28,7 @@ import torch
 script_path = Path(__file__).parent.resolve()
 sys.path.insert(0, str(script_path))
 
-from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, SincNet, StofNet, ZonziniNetLarge, ZonziniNetSmall, mask2coords  # noqa: E402
+from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, SincNet, StofNet, WaveUnet, ZonziniNetLarge, ZonziniNetSmall, mask2coords  # noqa: E402
 from stofnet_amd import config as config_mod                     # noqa: E402
 from stofnet_amd.metrics import toa_rmse                         # noqa: E402
 
@@ -127,6 +127,15 @@ def main(argv=None):
                 'cnn_act': ['leaky_relu', 'leaky_relu', 'leaky_relu', 'linear'], 'cnn_drop': [0.0, 0.0, 0.0, 0.0],
                 'use_sinc': True}
         model = SincNet(opts)
+        cfg.evaluate = True                                               # inference only on the gfx950 path
+    elif name == 'unet':                                                  # main.py:44-46,159-160
+        cfg.rf_scale_factor = cfg.rf_scale_factor * cfg.upsample_factor
+        cfg.upsample_factor = 1
+        n_layers = 2 if 'chirp' in str(cfg.data_dir).lower() else 10
+        if int(frames.shape[-1]) % (1 << n_layers):
+            raise ValueError(f'model=unet with n_layers={n_layers} needs a frame length that is a multiple of '
+                             f'{1 << n_layers} (got {int(frames.shape[-1])} samples)')
+        model = WaveUnet(n_layers=n_layers, channels_interval=16)
         cfg.evaluate = True                                               # inference only on the gfx950 path
     elif name == 'gradpeak':
         chirp = 'chirp' in str(cfg.data_dir).lower()
@@ -300,7 +309,7 @@ def evaluate(model, name, frames, gt, cfg, log=None):
             torch.cuda.synchronize()
             tic = time.perf_counter()
             out = model(frame)
-            if name in ('stofnet', 'edsr', 'espcn', 'sincnet'):          # main.py:318-320
+            if name in ('stofnet', 'edsr', 'espcn', 'sincnet', 'unet'):          # main.py:318-320
                 es = mask2coords(out, window_size=cfg.nms_win_size, threshold=cfg.th,
                                  upsample_factor=cfg.upsample_factor)
             else:

@@ -3,9 +3,12 @@
 inference only) run on the gfx950 kernels (stofnet_amd); EDSR_1D(1, 64, B, r | 64) and ESPCN_1D(r <= 64) run inference
 on the gfx950 kernels of csrc/riders.hip and keep the stock ATen route with the SampleShuffle1D kernel for training and
 for other widths (stofnet_amd/baselines.py); SincNet runs on the gfx950 kernels for the option dict of
-main.py (inference only; SincNet() without options raises NotImplementedError); the other comparison networks of the
-paper's table (Kuleshov, WaveUnet) are outside the accelerated path and raise when constructed."""
-from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, SincNet, StofNet, ZonziniNetLarge, ZonziniNetSmall  # noqa: F401
+main.py (inference only; SincNet() without options raises NotImplementedError); WaveUnet(n_layers = 1 .. 12,
+channels_interval=16), the configuration of main.py, runs inference on the gfx950 kernels of csrc/waveunet.hip and trains
+on the stock ATen route (stofnet_amd/waveunet.py; another channels_interval, the reference's default WaveUnet() included,
+raises NotImplementedError); the remaining comparison network of the paper's table (Kuleshov) is outside the accelerated
+path and raises when constructed."""
+from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, SincNet, StofNet, WaveUnet, ZonziniNetLarge, ZonziniNetSmall  # noqa: F401
 from stofnet_amd.stofnet import SemiGlobalBlock  # noqa: F401
 
 
@@ -19,4 +22,3 @@ def _out_of_scope(name):
 
 
 Kuleshov = _out_of_scope('Kuleshov')
-WaveUnet = _out_of_scope('WaveUnet')

@@ -9,3 +9,4 @@ from .gradpeak import GradPeak, toa_detect, grad_peak_detect  # noqa: F401
 from .baselines import EDSR_1D, ESPCN_1D               # noqa: F401
 from .zonzini import ZonziniNetSmall, ZonziniNetLarge  # noqa: F401
 from .sincnet import SincNet                         # noqa: F401
+from .waveunet import WaveUnet                       # noqa: F401

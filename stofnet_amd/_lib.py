@@ -54,6 +54,10 @@ class EspcnDesc(ctypes.Structure):
     _fields_ = [('upscale_factor', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class WaveUnetDesc(ctypes.Structure):
+    _fields_ = [('n_layers', ctypes.c_int32), ('channels_interval', ctypes.c_int32)]
+
+
 class AugmentDesc(ctypes.Structure):
     _fields_ = [('seed', ctypes.c_uint64), ('crop_ratio', ctypes.c_double), ('snr_db', ctypes.c_double),
                 ('normalize', ctypes.c_int32), ('add_noise', ctypes.c_int32), ('rank', ctypes.c_uint32),
@@ -151,6 +155,11 @@ _SIGNATURES = {
     'stof_espcn_pack_weights': (_c.c_int, [_c.POINTER(EspcnDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
     'stof_espcn_forward': (_c.c_int, [_c.POINTER(EspcnDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
                                       _c.c_void_p, _c.c_void_p]),
+    'stof_waveunet_packed_bytes': (_c.c_size_t, [_c.POINTER(WaveUnetDesc)]),
+    'stof_waveunet_pack_weights': (_c.c_int, [_c.POINTER(WaveUnetDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
+    'stof_waveunet_workspace_bytes': (_c.c_size_t, [_c.POINTER(WaveUnetDesc), _c.c_int64, _c.c_int64]),
+    'stof_waveunet_forward': (_c.c_int, [_c.POINTER(WaveUnetDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     'stof_iq2rf': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _c.c_double,
                               _c.c_int32, _c.c_void_p]),
     'stof_augment': (_c.c_int, [_c.POINTER(AugmentDesc), _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p,
