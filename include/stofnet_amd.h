@@ -447,6 +447,38 @@ size_t stof_waveunet_workspace_bytes(const stof_waveunet_desc* desc, int64_t N, 
 int stof_waveunet_forward(const stof_waveunet_desc* desc, const float* x, int64_t N, int64_t L, const void* packed, float* y,
                           float* bottleneck, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Kuleshov (models/kuleshov.py with num_layers = 4, `main.py model=kuleshov`), inference in exact fp32 with eval-mode
+ * BatchNorm as a per-channel affine computed by the host packer in double.  Served: input_length >= 641 (the
+ * shortest row for which every convolution has an output), output_length >= 1.  Conventions as for stof_edsr_*;
+ * anything outside the served range -> STOF_ERR_BAD_ARG (0 from the size functions), N = 0 -> STOF_OK without a
+ * launch, N x (length of the last concatenation) >= 2^31 - 256 -> STOF_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+typedef struct stof_kuleshov_desc {
+    int64_t input_length;        /* L: rows are cropped to their first L samples                                      */
+    int64_t output_length;       /* O: outputs of output_fc                                                           */
+    double bn_eps;               /* eps of every BatchNorm1d (torch default 1e-5)                                     */
+    int32_t tile_variant;        /* 0: the wave tile of each convolution is chosen by its size; 1, 2, 3: every
+                                  * convolution runs the 32 x 32, 32 x 128 or 64 x 128 wave tile (bitwise the same)  */
+    int32_t reserved;            /* 0                                                                                 */
+} stof_kuleshov_desc;
+/* params = 54 host pointers, the state dict in module order without the num_batches_tracked entries: per down block
+ * i = 0..3 down_conv{i}.weight, .bias, down_bn{i}.weight, .bias, .running_mean, .running_var; bottleneck.weight,
+ * .bias; per up block the same six of up_conv{i} / up_bn{i}; final_conv.weight (2,128,9), .bias; output_fc.weight
+ * (O, fc_dim), .bias.  The blob layout is documented in csrc/kuleshov.hip.                                          */
+size_t stof_kuleshov_packed_bytes(const stof_kuleshov_desc* desc);
+int stof_kuleshov_pack_weights(const stof_kuleshov_desc* desc, const float* const* params, void* out, size_t out_bytes);
+/* The four concatenation buffers, the bottleneck map and the Linear layer's input for N rows (0 for a bad desc or
+ * N <= 0); about 5.4 MB per row at L = 2000.                                                                        */
+size_t stof_kuleshov_workspace_bytes(const stof_kuleshov_desc* desc, int64_t N);
+/* x: N rows of at least L samples, x_row_stride (>= L) floats apart -> y[N, 1, O].  Optional taps (NULL = not
+ * written), channel-last: bottleneck [N, B, 512] = the output of bottleneck_last; final_in [N, Lc3, 128] = the input
+ * of final_conv (shuffled up_conv3 output, then down block 0's output); final_out [N, F, 2] = final_conv's output =
+ * the Linear layer's input.  Launches 12 kernels on `stream`.                                                       */
+int stof_kuleshov_forward(const stof_kuleshov_desc* desc, const float* x, int64_t N, int64_t x_row_stride,
+                          const void* packed, float* y, float* bottleneck, float* final_in, float* final_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* toa_rmse (utils/metrics.py:9-41): gt[N, G], es[N, E] fp32 with 0/NaN/inf as padding ->
  * out[N, 7] = (rmse, precision, recall, jaccard, tp, fp, fn).                  */
 int stof_toa_rmse(const float* gt, const float* es, int64_t N, int64_t G, int64_t E, float tol,

@@ -3,7 +3,7 @@
 (reference main.py:29-34,133-177,292-347), running the MI355X-native hot path.
 
 What it keeps: config.yaml + CLI merge, seeding (main.py:39-41), the model switch
-(stofnet / edsr / espcn / zonzini / sincnet / unet / gradpeak, main.py:133-167), checkpoint lookup by file-name prefix with strict
+(stofnet / edsr / espcn / zonzini / kuleshov / sincnet / unet / gradpeak, main.py:133-167), checkpoint lookup by file-name prefix with strict
 load_state_dict (main.py:173-177), the eval loop's `model(frame)` -> `mask2coords` ->
 `toa_rmse` sequence (main.py:314,320,347), and with `evaluate=False` the training loop
 (main.py:199-289: Gaussian-mask loss, AdamW, CosineAnnealingLR per epoch, EarlyStopping on the
@@ -28,7 +28,7 @@ import torch
 script_path = Path(__file__).parent.resolve()
 sys.path.insert(0, str(script_path))
 
-from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, SincNet, StofNet, WaveUnet, ZonziniNetLarge, ZonziniNetSmall, mask2coords  # noqa: E402
+from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, Kuleshov, SincNet, StofNet, WaveUnet, ZonziniNetLarge, ZonziniNetSmall, mask2coords  # noqa: E402
 from stofnet_amd import config as config_mod                     # noqa: E402
 from stofnet_amd.metrics import toa_rmse                         # noqa: E402
 
@@ -114,6 +114,9 @@ def main(argv=None):
         cfg.evaluate = True
     elif name == 'zonzini':                                               # main.py:135-136: Small on chirp data, else Large
         model = ZonziniNetSmall() if 'chirp' in str(cfg.data_dir).lower() else ZonziniNetLarge()
+        cfg.evaluate = True                                               # inference only on the gfx950 path
+    elif name == 'kuleshov':                                              # main.py:137-138
+        model = Kuleshov(input_length=int(frames.shape[-1]), output_length=int(frames.shape[-1]) * int(cfg.upsample_factor))
         cfg.evaluate = True                                               # inference only on the gfx950 path
     elif name == 'sincnet':                                               # main.py:143-158
         if cfg.fs is None:
@@ -309,7 +312,7 @@ def evaluate(model, name, frames, gt, cfg, log=None):
             torch.cuda.synchronize()
             tic = time.perf_counter()
             out = model(frame)
-            if name in ('stofnet', 'edsr', 'espcn', 'sincnet', 'unet'):          # main.py:318-320
+            if name in ('stofnet', 'edsr', 'espcn', 'kuleshov', 'sincnet', 'unet'):          # main.py:318-320
                 es = mask2coords(out, window_size=cfg.nms_win_size, threshold=cfg.th,
                                  upsample_factor=cfg.upsample_factor)
             else:

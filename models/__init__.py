@@ -6,19 +6,9 @@ for other widths (stofnet_amd/baselines.py); SincNet runs on the gfx950 kernels 
 main.py (inference only; SincNet() without options raises NotImplementedError); WaveUnet(n_layers = 1 .. 12,
 channels_interval=16), the configuration of main.py, runs inference on the gfx950 kernels of csrc/waveunet.hip and trains
 on the stock ATen route (stofnet_amd/waveunet.py; another channels_interval, the reference's default WaveUnet() included,
-raises NotImplementedError); the remaining comparison network of the paper's table (Kuleshov) is outside the accelerated
-path and raises when constructed."""
-from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, SincNet, StofNet, WaveUnet, ZonziniNetLarge, ZonziniNetSmall  # noqa: F401
+raises NotImplementedError); Kuleshov(input_length >= 641, output_length), the last comparison network of the paper's
+table, runs inference on the gfx950 kernels of csrc/kuleshov.hip and trains on the stock ATen route
+(stofnet_amd/kuleshov.py; num_layers other than 4, for which the reference's forward fails too, and Kuleshov() without
+lengths raise NotImplementedError)."""
+from stofnet_amd import EDSR_1D, ESPCN_1D, GradPeak, Kuleshov, SincNet, StofNet, WaveUnet, ZonziniNetLarge, ZonziniNetSmall  # noqa: F401
 from stofnet_amd.stofnet import SemiGlobalBlock  # noqa: F401
-
-
-def _out_of_scope(name):
-    class _Baseline:
-        def __init__(self, *args, **kwargs):
-            raise NotImplementedError(f'{name} is a comparison baseline of the reference and not part of the MI355X-native '
-                                      f'StofNet path (SURVEY.md section 2: out of scope)')
-    _Baseline.__name__ = _Baseline.__qualname__ = name
-    return _Baseline
-
-
-Kuleshov = _out_of_scope('Kuleshov')

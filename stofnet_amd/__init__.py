@@ -10,3 +10,4 @@ from .baselines import EDSR_1D, ESPCN_1D               # noqa: F401
 from .zonzini import ZonziniNetSmall, ZonziniNetLarge  # noqa: F401
 from .sincnet import SincNet                         # noqa: F401
 from .waveunet import WaveUnet                       # noqa: F401
+from .kuleshov import Kuleshov                       # noqa: F401

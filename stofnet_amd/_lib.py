@@ -58,6 +58,11 @@ class WaveUnetDesc(ctypes.Structure):
     _fields_ = [('n_layers', ctypes.c_int32), ('channels_interval', ctypes.c_int32)]
 
 
+class KuleshovDesc(ctypes.Structure):
+    _fields_ = [('input_length', ctypes.c_int64), ('output_length', ctypes.c_int64), ('bn_eps', ctypes.c_double),
+                ('tile_variant', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 class AugmentDesc(ctypes.Structure):
     _fields_ = [('seed', ctypes.c_uint64), ('crop_ratio', ctypes.c_double), ('snr_db', ctypes.c_double),
                 ('normalize', ctypes.c_int32), ('add_noise', ctypes.c_int32), ('rank', ctypes.c_uint32),
@@ -160,6 +165,11 @@ _SIGNATURES = {
     'stof_waveunet_workspace_bytes': (_c.c_size_t, [_c.POINTER(WaveUnetDesc), _c.c_int64, _c.c_int64]),
     'stof_waveunet_forward': (_c.c_int, [_c.POINTER(WaveUnetDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
                                          _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_kuleshov_packed_bytes': (_c.c_size_t, [_c.POINTER(KuleshovDesc)]),
+    'stof_kuleshov_pack_weights': (_c.c_int, [_c.POINTER(KuleshovDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
+    'stof_kuleshov_workspace_bytes': (_c.c_size_t, [_c.POINTER(KuleshovDesc), _c.c_int64]),
+    'stof_kuleshov_forward': (_c.c_int, [_c.POINTER(KuleshovDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     'stof_iq2rf': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _c.c_double,
                               _c.c_int32, _c.c_void_p]),
     'stof_augment': (_c.c_int, [_c.POINTER(AugmentDesc), _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p,
