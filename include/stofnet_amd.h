@@ -535,6 +535,22 @@ int stof_train_conv1_wgrad(const float* x, const float* g, const float* saved, f
  * dx[N][L] = out_scale * conv1^T(g * relu'(saved)), g and saved channel-last [N][L][64], w = conv1.weight (64,1,9).   */
 int stof_train_conv1_dgrad(const float* g, const float* saved, const float* w, float* dx, int64_t N, int64_t L,
                            float out_scale, void* stream);
+/* The same three for any width of models/stofnet.py:11,23 (in_channels Cin = 1..16, num_features F = 1..256; 9 taps, padding
+ * 4), exact fp32 on the vector pipe.  x and dx are NCL [N][Cin][L] as the module receives them, y / g / saved channel-last
+ * [N][L][F], w = conv1.weight (F,Cin,9), dw (F,Cin,9), db (F).  One fixed-order fmaf chain per output (bias, then input
+ * channels in order, taps 0..8 within each; dx: per tile of 64 output channels a chain over them in order, taps within, the
+ * tiles' sums added in order); the weight gradient adds per-group partials in a fixed order (no float atomics: bitwise
+ * repeatable), workspace = stof_train_conv1_c_wgrad_workspace_bytes.
+ * STOF_ERR_BAD_ARG on NULL or a width out of range, STOF_OK on an empty batch (dw / db zeroed), STOF_ERR_UNSUPPORTED where
+ * N L exceeds 2^31.  The 1 -> 64 entry points above stay what the shipped geometry runs.                                 */
+int stof_train_conv1_c(const float* x, const float* w, const float* b, float* y, int64_t N, int32_t Cin, int64_t L,
+                       int32_t F, void* stream);
+size_t stof_train_conv1_c_wgrad_workspace_bytes(int32_t Cin, int32_t F);
+int stof_train_conv1_c_wgrad(const float* x, const float* g, const float* saved, float* dw, float* db, int64_t N,
+                             int32_t Cin, int64_t L, int32_t F, float out_scale, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int stof_train_conv1_c_dgrad(const float* g, const float* saved, const float* w, float* dx, int64_t N, int32_t Cin,
+                             int64_t L, int32_t F, float out_scale, void* stream);
 /* SemiGlobalBlock pieces (models/stofnet.py:103,108-115), channel-last: MaxPool1d(scale, scale) with arg-max
  * (scale = sample_scale <= 256, P = floor(L / scale) windows), its routing backward (times lrelu' of the pre-pool
  * activation), nearest upsample x scale + pad (rem_half = (L - P*scale) / 2 on each side) + add and its backward.
@@ -582,6 +598,10 @@ int stof_train_upsample_add_c(const float* a, const float* e, float* out, int64_
                               int32_t rem_half, int32_t scale, int32_t C, void* stream);
 int stof_train_upsample_bwd(const float* g, const float* e, float* ge, int64_t N, int64_t L, int64_t P,
                             int32_t rem_half, int32_t scale, void* stream);
+/* The same for rows of C channels (any C >= 1): ge[N][P][C] = lrelu'(e) * the sum of g[N][L][C] over each window, taken in
+ * a fixed order.  STOF_ERR_UNSUPPORTED where N L exceeds 2^31.                                                            */
+int stof_train_upsample_bwd_c(const float* g, const float* e, float* ge, int64_t N, int64_t L, int64_t P,
+                              int32_t rem_half, int32_t scale, int32_t C, void* stream);
 /* Training forward on the fused sweep (split-fp16 mode; main.py:221 with the model in train mode): conv2 .. conv12 +
  * conv_last of models/stofnet.py:51-65 in ONE launch of the inference body sweep, which additionally writes every layer's
  * output to HBM for the backward pass -- instead of twelve stof_train_conv launches.

@@ -91,6 +91,9 @@ class SemiGlobalBlock(nn.Module):
 
 
 class StofNet(nn.Module):
+    # what forward() serves; every other geometry raises NotImplementedError with this text
+    SERVED = ('the gfx950 kernels serve num_features 1..256, in_channels 1..16, kernel_sizes [9, 1|3|5|7, 3], num_blocks >= 4, '
+              'semi_global_scale 1 or 2..256, upsample_factor 1..64')
 
     def __init__(self, upsample_factor=4, num_features=64, num_blocks=13, kernel_sizes=[9, 7, 3], in_channels=1,
                  semi_global_scale=80, weights_init=False, precision='auto', train_precision='f16x3'):
@@ -135,11 +138,22 @@ class StofNet(nn.Module):
                 and self.in_channels == 1 and (self.semi_global_scale == 1 or 2 <= self.semi_global_scale <= 256)
                 and 1 <= self.upsample_factor <= 64)
 
+    def _supported_wide(self):
+        """The geometries served at any width: `_supported()` with num_features 1..256 and in_channels 1..16 in place of 64 and
+        1 (models/stofnet.py:11,23-24,27,31).  Widths other than 64 / 1 run conv1 on the generic-width vector kernels and every
+        other layer on the channel-last MFMA kernels, layer by layer.  The first and last kernel sizes stay 9 and 3: their
+        paddings 4 and 1 are fixed in the reference (:23-24), so any other size changes the row length."""
+        ks = list(self.kernel_sizes)
+        return (1 <= self.num_features <= 256 and 1 <= self.in_channels <= 16 and self.num_blocks >= 4 and len(ks) == 3
+                and ks[0] == 9 and ks[2] == 3 and ks[1] in (1, 3, 5, 7)
+                and (self.semi_global_scale == 1 or 2 <= self.semi_global_scale <= 256) and 1 <= self.upsample_factor <= 64)
+
     def _fused_sweep(self):
-        """The persistent LDS-resident sweep serves the shipped geometry (13 blocks, 7-tap body, no SemiGlobalBlock or
-        sample_scale 80); any other semi_global_scale / num_blocks / body kernel size runs layer by layer on the
-        channel-last MFMA kernels of the training path."""
-        return self.semi_global_scale in (1, 80) and self.num_blocks == 13 and list(self.kernel_sizes) == [9, 7, 3]
+        """The persistent LDS-resident sweep serves the shipped geometry (64 features, one input channel, 13 blocks, 7-tap
+        body, no SemiGlobalBlock or sample_scale 80); any other width / semi_global_scale / num_blocks / body kernel size runs
+        layer by layer on the channel-last MFMA kernels of the training path."""
+        return (self.semi_global_scale in (1, 80) and self.num_blocks == 13 and list(self.kernel_sizes) == [9, 7, 3]
+                and self.num_features == 64 and self.in_channels == 1)
 
     def _param_list(self):
         ps = [self.conv1.weight, self.conv1.bias]
@@ -180,9 +194,10 @@ class StofNet(nn.Module):
 
     # ---- forward -------------------------------------------------------------
     def forward(self, x, _events=None):
-        if not self._supported():
-            raise NotImplementedError('the gfx950 kernels take 64 features, 1 input channel, kernel_sizes [9, 1|3|5|7, 3], '
-                                      'num_blocks >= 4, semi_global_scale 1 or 2..256')
+        if not (self._supported() or self._supported_wide()):
+            raise NotImplementedError(f'StofNet(num_features={self.num_features}, in_channels={self.in_channels}, kernel_sizes='
+                                      f'{list(self.kernel_sizes)}, num_blocks={self.num_blocks}, semi_global_scale='
+                                      f'{self.semi_global_scale}, upsample_factor={self.upsample_factor}): ' + self.SERVED)
         _lib.require_device(x, 'x')
         if x.dim() != 3 or x.shape[1] != self.in_channels:
             raise RuntimeError(f'expected input [N, {self.in_channels}, L], got {list(x.shape)}')
@@ -233,12 +248,13 @@ class StofNet(nn.Module):
         if key not in self._engines:
             self._engines[key] = TrainEngine(dev, self.upsample_factor, self.semi_global_block is not None, precision,
                                              scale=self.semi_global_scale if self.semi_global_block is not None else 80,
-                                             num_blocks=self.num_blocks, body_kernel=list(self.kernel_sizes)[1])
+                                             num_blocks=self.num_blocks, body_kernel=list(self.kernel_sizes)[1],
+                                             num_features=self.num_features, in_channels=self.in_channels)
         return self._engines[key]
 
     def _forward_layerwise(self, x):
-        """Inference for a semi_global_scale other than 80, a num_blocks other than 13 or a body kernel other than 7
-        (models/stofnet.py:11 accepts any): every layer on the
+        """Inference for a semi_global_scale other than 80, a num_blocks other than 13, a body kernel other than 7, a
+        num_features other than 64 or more than one input channel (models/stofnet.py:11 accepts any): every layer on the
         channel-last MFMA kernels, activations dropped as soon as the next layer has consumed them.  'auto' maps to the
         exact fp32 mode here (the range guard lives in the fused sweep)."""
         if x.shape[0] == 0:

@@ -131,8 +131,8 @@ class SavedForward:
     the body ran as the fused sweep, and that sweep wrote its dumps as split rows.  Fields a route does not use are None."""
     p: dict                     # name -> parameter tensor of this step
     bwd: _LazyRepack            # layer name -> flipped (data-gradient) weight image
-    x: torch.Tensor             # [N, L] input frame
-    a1: torch.Tensor            # [N, L, 64] relu(conv1)
+    x: torch.Tensor             # [N, L] input frame ([N, Cin, L] for in_channels > 1)
+    a1: torch.Tensor            # [N, L, F] relu(conv1)
     P: int                      # pooled length of the SemiGlobalBlock (0 without one)
     sweep: bool
     split: bool = False
@@ -157,7 +157,7 @@ class TrainEngine(LayerKernels):
     # batched weight-gradient launch) or layer by layer.  Within the sweep route the forward sweep decides whether the dumps
     # are split rows (`SavedForward.split`) and the backward follows it.
 
-    def __init__(self, dev, r, sgb, precision='fp32', scale=80, num_blocks=13, body_kernel=7):
+    def __init__(self, dev, r, sgb, precision='fp32', scale=80, num_blocks=13, body_kernel=7, num_features=64, in_channels=1):
         if precision not in ('fp32', 'f16x3'):
             raise ValueError("precision must be 'fp32' or 'f16x3'")
         super().__init__(dev, 1 if precision == 'f16x3' else 0)
@@ -172,13 +172,22 @@ class TrainEngine(LayerKernels):
             raise NotImplementedError('StofNet: the gfx950 layer kernels take body kernel sizes 1, 3, 5, 7')
         # SemiGlobalBlock geometry (models/stofnet.py:83-85): pool / upsample by `scale`, feat_scale = max(1, scale // 10)
         self.scale = int(scale)
-        self.cmid = 64 * max(1, self.scale // 10)
+        # models/stofnet.py:11,23: any num_features / in_channels.  The shipped 64 / 1 keeps its own kernels (conv1, up-sample
+        # backward, conv_last's data gradient, the sparse SemiGlobalBlock backward, the sweeps); every other width runs conv1 on
+        # the generic-width vector kernels (stof_train_conv1_c*) and the rest on the channel-last MFMA layer kernels, which pad
+        # to 64-channel blocks
+        self.F, self.cin = int(num_features), int(in_channels)
+        if not (1 <= self.F <= 256 and 1 <= self.cin <= 16):
+            raise NotImplementedError('StofNet: the gfx950 kernels take num_features 1..256 and in_channels 1..16')
+        self.wide = self.F != 64 or self.cin != 1
+        self.cmid = self.F * max(1, self.scale // 10)
         if self.sgb and not 2 <= self.scale <= 256:
             raise NotImplementedError('SemiGlobalBlock sample_scale must be in [2, 256] for the gfx950 kernels')
         # split-fp16 mode, shipped geometry: conv2..conv12 + conv_last of the forward run as ONE fused sweep that also writes
         # every layer's output for the backward pass (stof_train_sweep) instead of twelve layer launches, and the backward as
         # one sweep + one batched weight-gradient launch.
-        self.sweep = self.prec == 1 and (not self.sgb or self.scale == 80) and self.nb == 13 and self.kb == 7
+        self.sweep = (self.prec == 1 and (not self.sgb or self.scale == 80) and self.nb == 13 and self.kb == 7
+                      and not self.wide)
         self.sgb_sparse_taken = False       # bench.py: whether the last backward ran the sparse SemiGlobalBlock kernels
         self._bwd_overflow = None           # StofNetFunction: range-guard word of the last f16x3 backward, not yet read
 
@@ -192,14 +201,24 @@ class TrainEngine(LayerKernels):
         """models/stofnet.py:42-67, every activation kept for the backward pass (keep=False: inference, nothing kept).
         Returns (pred [N, L*r] = conv_last's channel-last output = the sample-shuffled prediction, SavedForward or None)."""
         _lib.require_device(frame, 'frame')
-        x = frame.detach().reshape(frame.shape[0], frame.shape[-1]).contiguous().float()
-        n, L = x.shape
+        if self.cin == 1:
+            x = frame.detach().reshape(frame.shape[0], frame.shape[-1]).contiguous().float()
+        else:
+            if frame.dim() != 3 or frame.shape[1] != self.cin:
+                raise RuntimeError(f'expected input [N, {self.cin}, L], got {list(frame.shape)}')
+            x = frame.detach().contiguous().float()                    # NCL, read as it is by stof_train_conv1_c
+        n, L = x.shape[0], x.shape[-1]
         P = L // self.scale if self.sgb else 0
         if self.sgb:
             raise_sgb_shape_error(L, self.scale)
-        a1 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().stof_train_conv1(_lib.ptr(x), _lib.ptr(p['conv1.weight']), _lib.ptr(p['conv1.bias']), _lib.ptr(a1),
-                                               n, L, self._st()), 'stof_train_conv1')
+        a1 = torch.empty((n, L, self.F), dtype=torch.float32, device=self.dev)
+        if self.wide:
+            _lib.check(_lib.lib().stof_train_conv1_c(_lib.ptr(x), _lib.ptr(p['conv1.weight'].contiguous()),
+                                                     _lib.ptr(p['conv1.bias'].contiguous()), _lib.ptr(a1), n, self.cin, L, self.F,
+                                                     self._st()), 'stof_train_conv1_c')
+        else:
+            _lib.check(_lib.lib().stof_train_conv1(_lib.ptr(x), _lib.ptr(p['conv1.weight']), _lib.ptr(p['conv1.bias']), _lib.ptr(a1),
+                                                   n, L, self._st()), 'stof_train_conv1')
         s = SavedForward(p=p, bwd=_LazyRepack(self, p, True) if keep else None, x=x, a1=a1, P=P, sweep=self.sweep)
         z = (self._forward_sweep if self.sweep else self._forward_layers)(s, keep)
         return z, (s if keep else None)
@@ -258,12 +277,12 @@ class TrainEngine(LayerKernels):
     def _forward_layers(self, s, keep):
         """models/stofnet.py:46-64 layer by layer for any num_blocks and body kernel; keep=False drops every activation as
         soon as nothing ahead reads it."""
-        p, nb, kb, r = s.p, self.nb, self.kb, self.r
+        p, nb, kb, r, F = s.p, self.nb, self.kb, self.r, self.F
         fwd = _LazyRepack(self, p, False)
         x0 = s.a1
         if self.sgb:
             x0, *kept = self._sgb_forward(s.a1, fwd[SG + 'contract_conv'], p[SG + 'contract_conv.bias'],
-                                          fwd[SG + 'expand_conv'], p[SG + 'expand_conv.bias'], self.scale)
+                                          fwd[SG + 'expand_conv'], p[SG + 'expand_conv.bias'], self.scale, width=F)
             if keep:
                 s.c, s.pooled, s.arg, s.e = kept
             del kept
@@ -273,16 +292,16 @@ class TrainEngine(LayerKernels):
         for i in range(2, nb - 1):
             nm = f'conv{i}'
             if i % 2:
-                v[i] = self._conv(v[i - 1], fwd[nm], p[nm + '.bias'], 64, 64, kb, ACT_NONE, residual=v[i - 2])
+                v[i] = self._conv(v[i - 1], fwd[nm], p[nm + '.bias'], F, F, kb, ACT_NONE, residual=v[i - 2])
                 if not keep:                   # v[i] is the running residual now; x0 stays for the long skip
                     v[i - 1] = None
                     if i > 3:
                         v[i - 2] = None
             else:
-                v[i] = self._conv(v[i - 1], fwd[nm], p[nm + '.bias'], 64, 64, kb, ACT_LRELU)
+                v[i] = self._conv(v[i - 1], fwd[nm], p[nm + '.bias'], F, F, kb, ACT_LRELU)
         nm = f'conv{nb - 1}'
-        x6 = self._conv(v[nb - 2], fwd[nm], p[nm + '.bias'], 64, 64, kb, ACT_NONE, residual=x0)
-        z = self._conv(x6, fwd['conv_last'], p['conv_last.bias'], 64, r, 3, ACT_NONE)      # [N, L, r] == shuffled [N, L*r]
+        x6 = self._conv(v[nb - 2], fwd[nm], p[nm + '.bias'], F, F, kb, ACT_NONE, residual=x0)
+        z = self._conv(x6, fwd['conv_last'], p['conv_last.bias'], F, r, 3, ACT_NONE)      # [N, L, r] == shuffled [N, L*r]
         if keep:
             s.v, s.x6 = v, x6
         return z.view(x0.shape[0], x0.shape[1] * r)
@@ -292,20 +311,23 @@ class TrainEngine(LayerKernels):
         """Backward pass from dpred [N, L*r] = gscale * dloss/dpred (gscale a power of two: the f16x3 data-gradient
         convolutions would otherwise work on fp16 subnormals; the weight-gradient kernels multiply by 1/gscale, exact).
         Writes every parameter gradient into the tensors of `g` (name -> tensor of the parameter's shape) and, if `dx`
-        [N, L] is given, the gradient with respect to the input frame into it.  Reads its route off `saved`."""
-        lib, st, r, split = _lib.lib(), self._st(), self.r, saved.split
-        n, L = saved.x.shape
+        [N, L] ([N, Cin, L] for in_channels > 1) is given, the gradient with respect to the input frame into it.  Reads its route off `saved`."""
+        lib, st, r, split, F = _lib.lib(), self._st(), self.r, saved.split, self.F
+        n, L = saved.x.shape[0], saved.x.shape[-1]
         inv = 1.0 / float(gscale)
         dz = dpred.view(n, L, r)
-        self._wgrad(saved.x6, dz, g['conv_last.weight'], g['conv_last.bias'], 64, r, 3, inv)
+        self._wgrad(saved.x6, dz, g['conv_last.weight'], g['conv_last.bias'], F, r, 3, inv)
         # conv_last's data gradient: r input channels would be padded to a 64-channel block by the layer kernels.  Split route:
         # g6 is a split-row tensor as well (the backward sweep's input, conv12's output gradient for the weight-gradient launch
         # and the long-skip join all take it as such)
-        g6 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
-        code = (lib.stof_train_conv_last_dgrad_split if split else lib.stof_train_conv_last_dgrad)(
-            _lib.ptr(dz.contiguous()), _lib.ptr(saved.p['conv_last.weight'].contiguous()), _lib.ptr(g6), n, L, r, st)
+        # (the vector kernel is written for 64 features: any other width takes the layer kernel)
+        code = _lib.STOF_ERR_UNSUPPORTED
+        if F == 64:
+            g6 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
+            code = (lib.stof_train_conv_last_dgrad_split if split else lib.stof_train_conv_last_dgrad)(
+                _lib.ptr(dz.contiguous()), _lib.ptr(saved.p['conv_last.weight'].contiguous()), _lib.ptr(g6), n, L, r, st)
         if code == _lib.STOF_ERR_UNSUPPORTED:
-            g6 = self._conv(dz, saved.bwd['conv_last'], None, r, 64, 3)
+            g6 = self._conv(dz, saved.bwd['conv_last'], None, r, F, 3)
             if split:
                 g6f, g6 = g6, torch.empty_like(g6)
                 _lib.check(lib.stof_train_to_split_rows(_lib.ptr(g6f), _lib.ptr(g6), n * L, st), 'stof_train_to_split_rows')
@@ -361,32 +383,46 @@ class TrainEngine(LayerKernels):
         # the residual add two layers on); its transposed convolution, masked with lrelu'(v[i-1]), is u = the gradient before
         # the activation of the even layer i-1; that layer's transposed convolution plus gg (the residual path) is the total
         # gradient of v[i-2].
-        v, bwd, kb = saved.v, saved.bwd, self.kb
+        v, bwd, kb, F = saved.v, saved.bwd, self.kb, self.F
         m = self.nb - 2                                                           # last layer of the loop (:52)
         second_last = f'conv{self.nb - 1}'
-        self._wgrad(v[m], g6, g[second_last + '.weight'], g[second_last + '.bias'], 64, 64, kb, inv)
+        self._wgrad(v[m], g6, g[second_last + '.weight'], g[second_last + '.bias'], F, F, kb, inv)
         if m % 2:
-            gg, u = self._conv(g6, bwd[second_last], None, 64, 64, kb), None        # d/dv[m], v[m] a residual state
+            gg, u = self._conv(g6, bwd[second_last], None, F, F, kb), None        # d/dv[m], v[m] a residual state
         else:
-            gg, u = None, self._conv(g6, bwd[second_last], None, 64, 64, kb, ACT_LRELU, saved=v[m])
+            gg, u = None, self._conv(g6, bwd[second_last], None, F, F, kb, ACT_LRELU, saved=v[m])
         for i in range(m, 1, -1):
             nm = f'conv{i}'
             if i % 2:
-                self._wgrad(v[i - 1], gg, g[nm + '.weight'], g[nm + '.bias'], 64, 64, kb, inv)
-                u = self._conv(gg, bwd[nm], None, 64, 64, kb, ACT_LRELU, saved=v[i - 1])
+                self._wgrad(v[i - 1], gg, g[nm + '.weight'], g[nm + '.bias'], F, F, kb, inv)
+                u = self._conv(gg, bwd[nm], None, F, F, kb, ACT_LRELU, saved=v[i - 1])
             else:
-                self._wgrad(v[i - 1], u, g[nm + '.weight'], g[nm + '.bias'], 64, 64, kb, inv)
-                gg = self._conv(u, bwd[nm], None, 64, 64, kb, residual=gg)      # (gg None for the loop's last layer)
+                self._wgrad(v[i - 1], u, g[nm + '.weight'], g[nm + '.bias'], F, F, kb, inv)
+                gg = self._conv(u, bwd[nm], None, F, F, kb, residual=gg)      # (gg None for the loop's last layer)
         return gg
 
     def _backward_sgb(self, saved, g_x0, g, inv):
         """SemiGlobalBlock backward from g_x0 = dL/d(block output): fills the gradients of both convolutions and returns
         dL/d relu(conv1), the residual path included."""
         lib, st = _lib.lib(), self._st()
-        (n, L), P, a1, bwd = saved.x.shape, saved.P, saved.a1, saved.bwd
+        n, L, P, a1, bwd = saved.x.shape[0], saved.x.shape[-1], saved.P, saved.a1, saved.bwd
         e, pooled, arg = saved.e, saved.pooled, saved.arg
-        S, cm = self.scale, self.cmid
+        S, cm, F = self.scale, self.cmid, self.F
         gw, gb = g[SG + 'contract_conv.weight'], g[SG + 'contract_conv.bias']
+        if F != 64:
+            # any other width: the up-sample backward for rows of F channels, then the dense route -- the sparse kernels below
+            # and stof_train_upsample_bwd are written for rows of 64 channels
+            ge = torch.empty((n, P, F), dtype=torch.float32, device=self.dev)
+            _lib.check(lib.stof_train_upsample_bwd_c(_lib.ptr(g_x0), _lib.ptr(e), _lib.ptr(ge), n, L, P, (L - S * P) // 2, S, F, st),
+                       'stof_train_upsample_bwd_c')
+            self._wgrad(pooled, ge, g[SG + 'expand_conv.weight'], g[SG + 'expand_conv.bias'], cm, F, 5, inv)
+            gpool = self._conv(ge, bwd[SG + 'expand_conv'], None, F, cm, 5)
+            gc = torch.empty((n, L, cm), dtype=torch.float32, device=self.dev)
+            _lib.check(lib.stof_train_pool_bwd(_lib.ptr(gpool), _lib.ptr(arg), _lib.ptr(saved.c), _lib.ptr(pooled), _lib.ptr(gc),
+                                               n, L, P, cm, S, st), 'stof_train_pool_bwd')
+            self._wgrad(a1, gc, gw, gb, F, cm, 5, inv)
+            self.sgb_sparse_taken = False
+            return self._conv(gc, bwd[SG + 'contract_conv'], None, cm, F, 5, residual=g_x0)
         ge = torch.empty((n, P, 64), dtype=torch.float32, device=self.dev)
         _lib.check(lib.stof_train_upsample_bwd(_lib.ptr(g_x0), _lib.ptr(e), _lib.ptr(ge), n, L, P, (L - S * P) // 2, S, st),
                    'stof_train_upsample_bwd')
@@ -423,7 +459,16 @@ class TrainEngine(LayerKernels):
     def _backward_conv1(self, saved, g_a1, g, inv, dx):
         """conv1's weight gradient from g_a1 masked with relu'(a1) and, if `dx` is given, d loss / d frame."""
         lib, st = _lib.lib(), self._st()
-        n, L = saved.x.shape
+        n, L = saved.x.shape[0], saved.x.shape[-1]
+        if self.wide:
+            ws1 = self._scratch('_conv1_c_ws', lib.stof_train_conv1_c_wgrad_workspace_bytes(self.cin, self.F))
+            _lib.check(lib.stof_train_conv1_c_wgrad(_lib.ptr(saved.x), _lib.ptr(g_a1), _lib.ptr(saved.a1), _lib.ptr(g['conv1.weight']),
+                                                    _lib.ptr(g['conv1.bias']), n, self.cin, L, self.F, inv, _lib.ptr(ws1), ws1.numel(),
+                                                    st), 'stof_train_conv1_c_wgrad')
+            if dx is not None:                  # [N, Cin, L], as the module received the frame
+                _lib.check(lib.stof_train_conv1_c_dgrad(_lib.ptr(g_a1), _lib.ptr(saved.a1), _lib.ptr(saved.p['conv1.weight'].contiguous()),
+                                                        _lib.ptr(dx), n, self.cin, L, self.F, inv, st), 'stof_train_conv1_c_dgrad')
+            return
         ws1 = torch.empty(lib.stof_train_conv1_wgrad_workspace_bytes(), dtype=torch.uint8, device=self.dev)
         _lib.check(lib.stof_train_conv1_wgrad(_lib.ptr(saved.x), _lib.ptr(g_a1), _lib.ptr(saved.a1), _lib.ptr(g['conv1.weight']),
                                               _lib.ptr(g['conv1.bias']), n, L, inv, _lib.ptr(ws1), ws1.numel(), st),
@@ -457,7 +502,7 @@ class StofNetFunction(torch.autograd.Function):
         if saved is None:
             raise RuntimeError('Trying to backward through the graph a second time: the saved activations of '
                                'StofNet.forward have been freed')
-        n, L = saved.x.shape
+        n, L = saved.x.shape[0], saved.x.shape[-1]
         m = L * engine.r
         with torch.cuda.device(engine.dev):
             dpred = grad_out.detach().reshape(n, m).contiguous().float()
@@ -493,7 +538,7 @@ class StofNetFunction(torch.autograd.Function):
                 off += k
             dx = None
             if ctx.needs_input_grad[0]:                 # d loss / d frame: the reference's autograd yields it (models/stofnet.py:45)
-                dx = torch.empty((n, L), dtype=torch.float32, device=engine.dev)
+                dx = torch.empty_like(saved.x)                    # [N, L], or [N, Cin, L] for in_channels > 1
             engine._backward_saved(saved, dpred, g, gscale, dx)
             if engine.prec == 1:
                 # Range guard of the split-fp16 backward, without a second host read: a non-finite gradient zeroes this step's
@@ -505,7 +550,7 @@ class StofNetFunction(torch.autograd.Function):
                     dx.masked_fill_(bad, 0.0)
                 engine._bwd_overflow = bad.float().reshape(1)
         ctx.saved = None
-        return (None if dx is None else dx.view(n, 1, L), None, None) + tuple(g[name] for name in ctx.names)
+        return (None if dx is None else dx.view(n, engine.cin, L), None, None) + tuple(g[name] for name in ctx.names)
 
 
 class StofNetTrainer(TrainEngine):
@@ -515,14 +560,15 @@ class StofNetTrainer(TrainEngine):
 
     def __init__(self, model: StofNet, lr=5e-4, weight_decay=1e-8, lambda_value=1e-2, mask_amplitude=20,
                  kernel_size=7, sigma=1, betas=(0.9, 0.999), eps=1e-8, process_group=None, precision='f16x3'):
-        if not model._supported():
-            raise NotImplementedError('this StofNet geometry has no gfx950 kernels (see StofNet._supported)')
+        if not (model._supported() or model._supported_wide()):
+            raise NotImplementedError('this StofNet geometry has no gfx950 kernels: ' + model.SERVED)
         if kernel_size != 7:
             raise NotImplementedError('the loss kernel implements the 7-tap blur of config.yaml:23')
         params = list(model.named_parameters())
         super().__init__(params[0][1].device, model.upsample_factor, model.semi_global_block is not None, precision,
                          scale=model.semi_global_scale if model.semi_global_block is not None else 80,
-                         num_blocks=model.num_blocks, body_kernel=list(model.kernel_sizes)[1])
+                         num_blocks=model.num_blocks, body_kernel=list(model.kernel_sizes)[1],
+                         num_features=model.num_features, in_channels=model.in_channels)
         self.model = model
         self.lr, self.wd, self.betas, self.eps = float(lr), float(weight_decay), betas, float(eps)
         self.lam, self.amp = float(lambda_value), float(mask_amplitude)
@@ -555,7 +601,7 @@ class StofNetTrainer(TrainEngine):
 
     # ---- forward + loss + backward -----------------------------------------------------------
     def forward_backward(self, frame: torch.Tensor, gt_true: torch.Tensor):
-        """frame [N,1,L] fp32, gt_true [N,1,G] int64 (round(gt_sample * r), main.py:218).  Fills the
+        """frame [N,Cin,L] fp32, gt_true [N,1,G] int64 (round(gt_sample * r), main.py:218).  Fills the
         gradient buffer and returns (loss as a 0-d float64 device tensor, masks_pred [N,1,L*r])."""
         with torch.cuda.device(self.dev):
             self.flat_grad.zero_()
