@@ -17,74 +17,13 @@ parameter, so parameter edits are picked up on their own; rows are bitwise indep
 chunking under `max_workspace_bytes` does not show in the result."""
 import ctypes
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from ._kernel_route import _KernelRoute, _pack
 from .sample_shuffle import SampleShuffle1D
-
-
-class _KernelRoute:
-    """Shared by EDSR_1D and ESPCN_1D: route decision, error contract and the packed-weight cache of the HIP route."""
-
-    def _kernel_params(self):
-        return list(self.parameters())
-
-    def _config_supported(self):
-        raise NotImplementedError
-
-    def kernels_supported(self, x):
-        """True when `forward_kernels(x)` can run: x float32 [N, 1, L] on the ROCm device, every parameter float32 on
-        that device, and a configuration the kernels are built for."""
-        if not (isinstance(x, torch.Tensor) and x.device.type == 'cuda' and x.dtype == torch.float32 and x.dim() == 3
-                and x.shape[1] == 1 and self._config_supported()):
-            return False
-        return all(p.dtype == torch.float32 and p.device == x.device for p in self._kernel_params())
-
-    def _takes_kernels(self, x):
-        if not self.kernels_supported(x):
-            return False
-        return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._kernel_params())))
-
-    def _check_kernels(self, x):
-        name = type(self).__name__
-        _lib.require_device(x, 'x')
-        if x.dtype != torch.float32:
-            raise TypeError(f'{name}: x must be float32 (got {x.dtype}); the gfx950 kernels are fp32 only')
-        for p in self._kernel_params():
-            if p.dtype != torch.float32:
-                raise TypeError(f'{name}: parameters must be float32 (got {p.dtype}); the gfx950 kernels are fp32 only')
-            _lib.require_device(p, 'parameter')
-        if not self.kernels_supported(x):
-            raise RuntimeError(f'{name}: the gfx950 kernels need x of shape [N, 1, L] on the parameters\' device and '
-                               f'{self._KERNEL_CONFIG} (got x {list(x.shape)}); use forward_aten')
-
-    def invalidate_packed(self):
-        """Drop the packed weights (they are rebuilt on the next forward; parameter edits are also detected on their own)."""
-        self._packed = None
-        self._packed_key = None
-
-    def packed_weights(self, device):
-        params = self._kernel_params()
-        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
-        if getattr(self, '_packed', None) is None or self._packed_key != key:
-            host = [np.ascontiguousarray(p.detach().cpu().numpy(), dtype=np.float32) for p in params]
-            self._packed = self._pack(host).to(device)
-            self._packed_key = key
-        return self._packed
-
-
-def _pack(packed_bytes, pack_weights, desc, arrs, what):
-    n = int(packed_bytes(ctypes.byref(desc)))
-    if n == 0:
-        raise ValueError(f'{what}: unsupported configuration')
-    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in arrs]
-    ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    blob = torch.zeros(n, dtype=torch.uint8)
-    _lib.check(pack_weights(ctypes.byref(desc), ptrs, ctypes.c_void_p(blob.data_ptr()), n), what)
-    return blob
 
 
 def pack_edsr_weights(num_blocks, upscale_factor, params):
@@ -134,8 +73,6 @@ class EDSR_1D(_KernelRoute, nn.Module):
         self.conv_mid = nn.Conv1d(num_features, num_features, kernel_size=3, stride=1, padding=1)
         self.upscale = SampleShuffle1D(upscale_factor)
         self.conv_output = nn.Conv1d(num_features // upscale_factor, num_channels, kernel_size=3, stride=1, padding=1)
-        self._packed = None
-        self._packed_key = None
 
     def _config_supported(self):
         r = self.upscale.upsample_factor
@@ -144,9 +81,6 @@ class EDSR_1D(_KernelRoute, nn.Module):
 
     def _pack(self, host):
         return pack_edsr_weights(len(self.residual_blocks), self.upscale.upsample_factor, host)
-
-    def forward(self, x):
-        return self.forward_kernels(x) if self._takes_kernels(x) else self.forward_aten(x)
 
     def forward_kernels(self, x):
         """y [N, 1, L r] float32 on the gfx950 kernels (no autograd graph); raises where they do not apply."""
@@ -168,18 +102,14 @@ class EDSR_1D(_KernelRoute, nn.Module):
         packed = self.packed_weights(x.device)
         lib = _lib.lib()
         desc = _lib.EdsrDesc(len(self.residual_blocks), r)
-        per_row = int(lib.stof_edsr_workspace_bytes(ctypes.byref(desc), 1, L))
-        chunk = max(1, min(N, int(self.max_workspace_bytes) // per_row))
-        ws_bytes = int(lib.stof_edsr_workspace_bytes(ctypes.byref(desc), chunk, L))
-        with torch.cuda.device(x.device):
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-            stream = _lib.stream_ptr(x.device)
-            for r0 in range(0, N, chunk):
-                n = min(chunk, N - r0)
-                _lib.check(lib.stof_edsr_forward(
-                    ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), n, L, _lib.ptr(packed),
-                    ctypes.c_void_p(y[r0].data_ptr()), None if trunk is None else ctypes.c_void_p(trunk[r0].data_ptr()),
-                    _lib.ptr(ws), ws_bytes, stream), 'stof_edsr_forward')
+
+        def launch(r0, n, ws, ws_bytes, stream):
+            _lib.check(lib.stof_edsr_forward(
+                ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), n, L, _lib.ptr(packed),
+                ctypes.c_void_p(y[r0].data_ptr()), None if trunk is None else ctypes.c_void_p(trunk[r0].data_ptr()),
+                _lib.ptr(ws), ws_bytes, stream), 'stof_edsr_forward')
+
+        self._chunked(x.device, N, lambda n: int(lib.stof_edsr_workspace_bytes(ctypes.byref(desc), n, L)), launch)
         return y, trunk
 
     def forward_aten(self, x):
@@ -207,8 +137,6 @@ class ESPCN_1D(_KernelRoute, nn.Module):
                 std = 0.001 if m.in_channels == 32 else (2.0 / (m.out_channels * m.weight[0][0].numel())) ** 0.5
                 nn.init.normal_(m.weight.data, 0.0, std)
                 nn.init.zeros_(m.bias.data)
-        self._packed = None
-        self._packed_key = None
 
     def _config_supported(self):
         r = self.sample_shuffle.upsample_factor
@@ -216,9 +144,6 @@ class ESPCN_1D(_KernelRoute, nn.Module):
 
     def _pack(self, host):
         return pack_espcn_weights(self.sample_shuffle.upsample_factor, host)
-
-    def forward(self, x):
-        return self.forward_kernels(x) if self._takes_kernels(x) else self.forward_aten(x)
 
     def forward_kernels(self, x):
         """y [N, 1, L r] float32 on the gfx950 kernel (no autograd graph); raises where it does not apply."""

@@ -37,9 +37,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
+#include "mfma32_frag.h"
 #include "stof_common.h"
 
 namespace {
+
+using namespace stof_frag;
 
 constexpr int NL = 4;
 constexpr int NF[NL] = {128, 256, 512, 512};
@@ -56,11 +59,8 @@ constexpr int XS0 = 2 * T0 + 64;                // its LDS window (2 (T0 - 1) + 
 constexpr int FIN_T = 16;                       // positions per wave of ks_final_kernel
 constexpr int QU_WIDE = 1, QU_MID = 2, QU_NARROW = 4;   // K groups per step of the 64 x 128, 32 x 128 and 32 x 32 wave tile
 constexpr int FC_MT = 4;                        // M tiles (of 32 rows) per work-group of ks_fc_kernel
-constexpr int64_t ALIGN_F = 64;                 // float alignment of every packed section and workspace buffer (256 B)
 constexpr int NUM_PARAMS = 54;                  // see stof_kuleshov_pack_weights in include/stofnet_amd.h
 enum { EP_DOWN = 0, EP_BOTT = 1, EP_UP = 2 };
-
-int64_t align_up(int64_t v) { return (v + ALIGN_F - 1) / ALIGN_F * ALIGN_F; }
 
 struct Dims {
     int64_t L, O, D[NL], B, U[NL], Lc[NL], F, Kp, G, OT;
@@ -148,9 +148,6 @@ Work work(const Dims& d, int64_t N) {
 }
 
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : slope * v; }   // NaN stays NaN
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define MFMA32(a, b, acc) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (acc), 0, 0, 0)
 
 // ---------------------------------------------------------------------------------------------------------- down 0
 // Work-group (row n, outputs t0 .. t0 + 63): thread (c = tid & 127, half = tid >> 7) owns channel c of outputs
@@ -432,20 +429,6 @@ __global__ __launch_bounds__(256) void ks_fc_kernel(const float* __restrict__ fl
 }
 
 // --------------------------------------------------------------------------------------------------------- packing
-// Conv1d weight [Cout][Cin][fs] (torch layout) -> fragment order with k = tap Cin + ci
-void pack_frag(const float* w, int Cout, int Cin, int fs, float* out) {
-    const int64_t G = (int64_t)fs * Cin / 8;
-    for (int nt = 0; nt < Cout / 32; ++nt)
-        for (int64_t q = 0; q < G; ++q)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    const int oc = 32 * nt + (lane & 31);
-                    const int64_t k = 8 * q + 4 * (lane >> 5) + e;
-                    const int j = (int)(k / Cin), ci = (int)(k % Cin);
-                    out[((nt * G + q) * 64 + lane) * 4 + e] = w[((int64_t)oc * Cin + ci) * fs + j];
-                }
-}
-
 // bn = {weight, bias, running_mean, running_var}
 void bn_down(const float* const* bn, const float* bias, int C, double eps, float* ep) {
     for (int c = 0; c < C; ++c) {
@@ -503,16 +486,17 @@ extern "C" int stof_kuleshov_pack_weights(const stof_kuleshov_desc* desc, const 
         for (int j = 0; j < FS[0]; ++j) blob[o.w0 + j * C0 + c] = params[0][c * FS[0] + j];
     bn_down(params + 2, params[1], C0, eps, blob + o.ep0);
     for (int i = 1; i < NL; ++i) {
-        pack_frag(params[6 * i], NF[i], NF[i - 1], FS[i], blob + o.dfrag[i]);
+        pack_frag32(params[6 * i], NF[i], NF[i - 1], FS[i], NF[i - 1], NF[i] / 32, FS[i] * NF[i - 1] / 8, blob + o.dfrag[i]);
         bn_down(params + 6 * i + 2, params[6 * i + 1], NF[i], eps, blob + o.dep[i]);
     }
-    pack_frag(params[24], 512, 512, KB, blob + o.bfrag);
+    pack_frag32(params[24], 512, 512, KB, 512, 512 / 32, KB * 512 / 8, blob + o.bfrag);
     for (int c = 0; c < 512; ++c) {
         blob[o.bep + c] = params[25][c];
         blob[o.bep + 512 + c] = 1.f;
     }
     for (int i = 0; i < NL; ++i) {
-        pack_frag(params[26 + 6 * i], UP_COUT[i], UP_CIN[i], UP_FS[i], blob + o.ufrag[i]);
+        pack_frag32(params[26 + 6 * i], UP_COUT[i], UP_CIN[i], UP_FS[i], UP_CIN[i], UP_COUT[i] / 32, UP_FS[i] * UP_CIN[i] / 8,
+                    blob + o.ufrag[i]);
         bn_up(params + 26 + 6 * i + 2, params[26 + 6 * i + 1], UP_COUT[i], eps, blob + o.uep[i]);
     }
     // final_conv: weight [2][128][9] -> wf[oc][tap][ci]
@@ -521,21 +505,8 @@ extern "C" int stof_kuleshov_pack_weights(const stof_kuleshov_desc* desc, const 
             for (int j = 0; j < KB; ++j) blob[o.wf + (oc * KB + j) * C0 + ci] = params[50][(oc * C0 + ci) * KB + j];
     blob[o.bf] = params[51][0];
     blob[o.bf + 1] = params[51][1];
-    // output_fc: weight [O][2 F] -> fragments (the blob is zero where o >= O or k >= 2 F)
-    const float* const fw = params[52];
-    const int64_t K = 2 * d.F;
-    float* const ff = blob + o.fcfrag;
-    for (int64_t ot = 0; ot < d.OT; ++ot)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int64_t oc = 32 * ot + (lane & 31);
-            if (oc >= d.O) continue;
-            const float* const src = fw + oc * K;
-            for (int64_t q = 0; q < d.G; ++q)
-                for (int e = 0; e < 4; ++e) {
-                    const int64_t k = 8 * q + 4 * (lane >> 5) + e;
-                    if (k < K) ff[((ot * d.G + q) * 64 + lane) * 4 + e] = src[k];
-                }
-        }
+    // output_fc: weight [O][2 F] -> fragments, zero where o >= O or k >= 2 F
+    pack_frag32(params[52], d.O, 1, 2 * d.F, 1, d.OT, d.G, blob + o.fcfrag);
     memcpy(blob + o.fcb, params[53], sizeof(float) * (size_t)d.O);
     return STOF_OK;
 }

@@ -42,9 +42,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
+#include "mfma32_frag.h"
 #include "stof_common.h"
 
 namespace {
+
+using namespace stof_frag;
 
 constexpr int C = 64;                      // EDSR num_features
 constexpr int GAP = 1;                     // zero rows between waveforms (= the padding of every EDSR conv)
@@ -52,7 +55,6 @@ constexpr int KC = 3 * C;                  // K of the 64 -> 64 convs
 constexpr int GC = KC / 8;                 // K groups of 8
 constexpr int FRAG_C = 2 * GC * 64 * 4;    // floats of one 64 -> 64 weight in fragment order
 constexpr int64_t NARROW_M = 64 * 1024;    // below N L = this, waves of ed_conv_kernel own one N tile instead of two
-constexpr int64_t ALIGN_F = 64;            // float alignment of every packed section and workspace buffer (256 B)
 constexpr int MAX_BLOCKS = 1024;
 
 constexpr int ES_T = 126;                  // samples per work-group of es_kernel (a2 needs ES_T + 2 = 4 waves x 32 rows)
@@ -60,8 +62,6 @@ constexpr int ES_XS = ES_T + 8;            // staged x
 constexpr int ES_R1 = 68, ES_ROWS1 = ES_T + 4;    // a1: row stride (floats), rows t0 - 2 .. t0 + ES_T + 1
 constexpr int ES_R2 = 36, ES_ROWS2 = ES_T + 4;    // a2: rows t0 - 1 .. t0 + ES_T (+ 2 rows only the two unused outputs read)
 constexpr int ES_G2 = 3 * 64 / 8, ES_G3 = 3 * 32 / 8;
-
-int64_t align_up(int64_t v) { return (v + ALIGN_F - 1) / ALIGN_F * ALIGN_F; }
 
 // EDSR blob (floats, every section starts on a 256-byte boundary), B = num_blocks, Cq = 64 / r:
 //   cin   [4][64]                   rows 0..2 = conv_input.weight[c][0][tap], row 3 = conv_input.bias
@@ -120,9 +120,6 @@ bool es_desc_ok(const stof_espcn_desc* d) { return d && d->upscale_factor >= 1 &
 
 __device__ __forceinline__ float relu(float v) { return v < 0.f ? 0.f : v; }   // keeps NaN (v > 0 ? v : 0 would not)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define MFMA32(a, b, acc) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (acc), 0, 0, 0)
-
 // ------------------------------------------------------------------------------------------------------------- gaps
 __global__ __launch_bounds__(256) void ed_gaps_kernel(float* __restrict__ b0, float* __restrict__ b1, float* __restrict__ b2,
                                                       long long L, long long total) {
@@ -176,29 +173,7 @@ __global__ __launch_bounds__(256) void ed_conv_kernel(const float* __restrict__ 
     const int nt0 = blockIdx.y * NTW;
     const float4* bq = frag + (long long)nt0 * GC * 64 + lane;
     f32x16 acc[NTW] = {};
-    float4 av = *reinterpret_cast<const float4*>(a);
-    float4 bv[NTW];
-#pragma unroll
-    for (int nt = 0; nt < NTW; ++nt) bv[nt] = bq[(long long)nt * GC * 64];
-    for (int q = 0; q < GC; ++q) {
-        const float4 ca = av;
-        float4 cb[NTW];
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) cb[nt] = bv[nt];
-        if (q + 1 < GC) {
-            av = *reinterpret_cast<const float4*>(a + 8 * (q + 1));
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) bv[nt] = bq[((long long)nt * GC + q + 1) * 64];
-        }
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA32(ca.x, cb[nt].x, acc[nt]);
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA32(ca.y, cb[nt].y, acc[nt]);
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA32(ca.z, cb[nt].z, acc[nt]);
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA32(ca.w, cb[nt].w, acc[nt]);
-    }
+    mfma32_k_loop<NTW, GC>(a, bq, acc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const unsigned row = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -359,27 +334,7 @@ __global__ __launch_bounds__(256) void es_kernel(const float* __restrict__ x, lo
     }
 }
 
-// --------------------------------------------------------------------------------------------------------- packing
-// dense [32 nts][K] (k order of the GEMM) -> fragment order
-void pack_frag(const float* dense, int nts, int K, float* out) {
-    const int G = K / 8;
-    for (int nt = 0; nt < nts; ++nt)
-        for (int q = 0; q < G; ++q)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    const int oc = 32 * nt + (lane & 31), k = 8 * q + 4 * (lane >> 5) + e;
-                    out[(((int64_t)nt * G + q) * 64 + lane) * 4 + e] = dense[(int64_t)oc * K + k];
-                }
-}
-
-// weight [oc][cin][kt] -> dense [rows][kt * cin] with k = tap * cin + ci; rows >= oc stay zero
-void to_dense(const float* w, int oc, int rows, int cin, int kt, float* dense) {
-    memset(dense, 0, sizeof(float) * rows * kt * cin);
-    for (int o = 0; o < oc; ++o)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int j = 0; j < kt; ++j) dense[(int64_t)o * kt * cin + j * cin + ci] = w[((int64_t)o * cin + ci) * kt + j];
-}
-
+// -------------------------------------------------------------------------------------------------------- launches
 template <int NTW, bool RELU, bool RES>
 void launch_conv(dim3 grid, hipStream_t s, const float* in, unsigned M, unsigned L, const float* frag, const float* bias,
                  const float* res, float* out, float* dense) {
@@ -413,15 +368,11 @@ extern "C" int stof_edsr_pack_weights(const stof_edsr_desc* desc, const float* c
         for (int j = 0; j < 3; ++j) blob[o.cin + j * C + c] = params[0][c * 3 + j];
         blob[o.cin + 3 * C + c] = params[1][c];
     }
-    float* dense = static_cast<float*>(malloc(sizeof(float) * C * KC));
-    if (!dense) return STOF_ERR_WORKSPACE;
     for (int l = 0; l <= 2 * B; ++l) {                 // params 2 + 2 l, 3 + 2 l: block l / 2 conv1 | conv2, last conv_mid
         float* sec = blob + o.conv0 + (int64_t)l * (FRAG_C + C);
-        to_dense(params[2 + 2 * l], C, C, C, 3, dense);
-        pack_frag(dense, 2, KC, sec);
+        pack_frag32(params[2 + 2 * l], C, C, 3, C, 2, GC, sec);
         memcpy(sec + FRAG_C, params[3 + 2 * l], sizeof(float) * C);
     }
-    free(dense);
     const float* wo = params[np - 2];
     for (int c = 0; c < cq; ++c)
         for (int j = 0; j < 3; ++j) blob[o.cout + j * cq + c] = wo[c * 3 + j];
@@ -511,15 +462,10 @@ extern "C" int stof_espcn_pack_weights(const stof_espcn_desc* desc, const float*
         for (int j = 0; j < 5; ++j) blob[o.c1 + j * 64 + c] = params[0][c * 5 + j];
         blob[o.c1 + 5 * 64 + c] = params[1][c];
     }
-    float* dense = static_cast<float*>(malloc(sizeof(float) * 64 * 192));
-    if (!dense) return STOF_ERR_WORKSPACE;
-    to_dense(params[2], 32, 32, 64, 3, dense);
-    pack_frag(dense, 1, 192, blob + o.frag2);
+    pack_frag32(params[2], 32, 64, 3, 64, 1, ES_G2, blob + o.frag2);
     memcpy(blob + o.b2, params[3], sizeof(float) * 32);
-    to_dense(params[4], r, 32 * nt, 32, 3, dense);
-    pack_frag(dense, nt, 96, blob + o.frag3);
+    pack_frag32(params[4], r, 32, 3, 32, nt, ES_G3, blob + o.frag3);      // output channels >= r are zero
     memcpy(blob + o.b3, params[5], sizeof(float) * r);
-    free(dense);
     return STOF_OK;
 }
 

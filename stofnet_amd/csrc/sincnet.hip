@@ -30,9 +30,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
+#include "mfma32_frag.h"
 #include "stof_common.h"
 
 namespace {
+
+using namespace stof_frag;
 
 constexpr int C = 128;                 // filters of layers 0..2
 constexpr int K0 = 1023;               // sinc taps
@@ -44,10 +47,7 @@ constexpr int TILE0 = 128;             // samples per work-group of sn_sinc_kern
 constexpr int XS0 = TILE0 + K0P;       // LDS image of sn_sinc_kernel: x[t0 - 511 .. t0 + 640]
 constexpr int OUT_T = 16;              // samples per wave of sn_out_kernel
 constexpr int64_t NARROW_M = 128 * 1024;   // below N L = this, waves of the MFMA kernels own one N tile instead of four
-constexpr int64_t ALIGN_F = 64;        // float alignment of every packed section and workspace buffer (256 B)
 constexpr int NUM_PARAMS = 24;         // see stof_sincnet_pack_weights in include/stofnet_amd.h
-
-int64_t align_up(int64_t v) { return (v + ALIGN_F - 1) / ALIGN_F * ALIGN_F; }
 
 // Packed blob (floats, every section starts on a 256-byte boundary):
 //   frag0 [4 N tiles][K0P / 8][64 lanes][4]        the synthesised filter bank, k = tap
@@ -83,9 +83,6 @@ bool desc_ok(const stof_sincnet_desc* d) {
 }
 
 __device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : 0.2f * v; }   // NaN: 0.2 * NaN = NaN
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define MFMA32(a, b, acc) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (acc), 0, 0, 0)
 
 // ------------------------------------------------------------------------------------------------------------- gaps
 __global__ __launch_bounds__(256) void sn_gaps_kernel(float* __restrict__ b0, float* __restrict__ b1, long long L,
@@ -172,29 +169,7 @@ __global__ __launch_bounds__(256) void sn_conv_kernel(const float* __restrict__ 
     const int nt0 = blockIdx.y * NTW;
     const float4* bq = frag + (long long)nt0 * G * 64 + lane;
     f32x16 acc[NTW] = {};
-    float4 av = *reinterpret_cast<const float4*>(a);
-    float4 bv[NTW];
-#pragma unroll
-    for (int nt = 0; nt < NTW; ++nt) bv[nt] = bq[(long long)nt * G * 64];
-    for (int q = 0; q < G; ++q) {
-        const float4 ca = av;
-        float4 cb[NTW];
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) cb[nt] = bv[nt];
-        if (q + 1 < G) {
-            av = *reinterpret_cast<const float4*>(a + 8 * (q + 1));
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) bv[nt] = bq[((long long)nt * G + q + 1) * 64];
-        }
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA32(ca.x, cb[nt].x, acc[nt]);
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA32(ca.y, cb[nt].y, acc[nt]);
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA32(ca.z, cb[nt].z, acc[nt]);
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA32(ca.w, cb[nt].w, acc[nt]);
-    }
+    mfma32_k_loop<NTW, G>(a, bq, acc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const unsigned row = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -271,18 +246,6 @@ void sinc_bank(double fs, const float* low_hz, const float* band_hz, double* ban
     }
 }
 
-// dense [C][K] (k order of the GEMM) -> fragment order
-void pack_frag(const float* dense, int K, float* out) {
-    const int G = K / 8;
-    for (int nt = 0; nt < 4; ++nt)
-        for (int q = 0; q < G; ++q)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    const int oc = 32 * nt + (lane & 31), k = 8 * q + 4 * (lane >> 5) + e;
-                    out[(((int64_t)nt * G + q) * 64 + lane) * 4 + e] = dense[(int64_t)oc * K + k];
-                }
-}
-
 // BN (eval) after a conv with bias `bias` (NULL: none): y = (acc + bias - mean) / sqrt(var + eps) * gamma + beta
 void bn_affine(const float* const* bn, const float* bias, int c, double eps, float* s, float* t) {
     const double sc = (double)bn[0][c] / sqrt((double)bn[3][c] + eps);
@@ -315,32 +278,17 @@ extern "C" int stof_sincnet_pack_weights(const stof_sincnet_desc* desc, const fl
     if (out_bytes < (size_t)o.total * sizeof(float)) return STOF_ERR_WORKSPACE;
     float* const blob = static_cast<float*>(out);
     memset(blob, 0, (size_t)o.total * sizeof(float));
-    const size_t dense_n = (size_t)C * K1 * C;         // the largest dense section
-    float* dense = static_cast<float*>(malloc(sizeof(float) * dense_n));
-    if (!dense) return STOF_ERR_WORKSPACE;
-    // layer 0: bank [C][1023] -> dense [C][1024] with a zero last tap
-    memset(dense, 0, sizeof(float) * dense_n);
+    // layer 0: bank [C][1][1023] -> k = tap, the last tap of the 1024 zero
     {
         float* bank = static_cast<float*>(malloc(sizeof(float) * C * K0));
-        if (!bank) { free(dense); return STOF_ERR_WORKSPACE; }
+        if (!bank) return STOF_ERR_WORKSPACE;
         stof_sincnet_filter_bank(desc, params[0], params[1], bank);
-        for (int c = 0; c < C; ++c)
-            for (int k = 0; k < K0; ++k) dense[(int64_t)c * K0P + k] = bank[(int64_t)c * K0 + k];
+        pack_frag32(bank, C, 1, K0, 1, C / 32, K0P / 8, blob + o.frag0);
         free(bank);
     }
-    pack_frag(dense, K0P, blob + o.frag0);
-    // layers 1, 2: weight [C][C][K] -> dense [C][K * C] with k = tap * C + ci
-    const int ks[2] = {K1, K2};
-    const int64_t frag_at[2] = {o.frag1, o.frag2};
-    for (int l = 0; l < 2; ++l) {
-        const float* w = params[2 + 2 * l];
-        const int K = ks[l];
-        for (int oc = 0; oc < C; ++oc)
-            for (int ci = 0; ci < C; ++ci)
-                for (int j = 0; j < K; ++j) dense[(int64_t)oc * K * C + j * C + ci] = w[((int64_t)oc * C + ci) * K + j];
-        pack_frag(dense, K * C, blob + frag_at[l]);
-    }
-    free(dense);
+    // layers 1, 2: weight [C][C][K] -> k = tap * C + ci
+    pack_frag32(params[2], C, C, K1, C, C / 32, K1 * C / 8, blob + o.frag1);
+    pack_frag32(params[4], C, C, K2, C, C / 32, K2 * C / 8, blob + o.frag2);
     // layer 3: weight [1][C][7] -> w3[tap][ci]
     for (int ci = 0; ci < C; ++ci)
         for (int j = 0; j < K3; ++j) blob[o.w3 + j * C + ci] = params[6][ci * K3 + j];

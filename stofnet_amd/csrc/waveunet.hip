@@ -49,18 +49,18 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include "mfma32_frag.h"
 #include "stof_common.h"
 
 namespace {
+
+using namespace stof_frag;
 
 constexpr int CI = 16;                     // channels_interval
 constexpr int MAX_LAYERS = 12;
 constexpr int TM = 64;                     // positions per work-group of wu_conv_kernel
 constexpr int CHUNK = 192;                 // channels per LDS pass
 constexpr int ENC_TAPS = 15, DEC_TAPS = 5;
-constexpr int64_t ALIGN_F = 64;
-
-int64_t align_up(int64_t v) { return (v + ALIGN_F - 1) / ALIGN_F * ALIGN_F; }
 
 bool wu_desc_ok(const stof_waveunet_desc* d) {
     return d && d->channels_interval == CI && d->n_layers >= 1 && d->n_layers <= MAX_LAYERS;

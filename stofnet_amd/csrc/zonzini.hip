@@ -21,9 +21,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
+#include "mfma32_frag.h"
 #include "stof_common.h"
 
 namespace {
+
+using namespace stof_frag;
 
 constexpr int KW = 10;                 // kernel_size of every conv
 constexpr int FC1 = 1024;              // fc1 width
@@ -31,7 +34,6 @@ constexpr int MAXL = 5;                // conv layers of the Large net
 constexpr int HEAD_ROWS = 16;          // rows per work-group of the head
 constexpr int HEAD_THREADS = FC1;     // one fc1 unit per thread
 constexpr int CONV_WAVES = 4;          // waves per work-group of zz_conv_kernel: 2 M tiles x 2 N tiles
-constexpr int64_t ALIGN_F = 64;        // float alignment of every packed section and workspace buffer (256 B)
 
 struct Geometry {
     int layers;
@@ -57,7 +59,6 @@ bool geometry(const stof_zonzini_desc* d, Geometry& g) {
     return true;
 }
 
-int64_t align_up(int64_t v) { return (v + ALIGN_F - 1) / ALIGN_F * ALIGN_F; }
 int ntiles(int c) { return (c + 31) / 32; }
 int64_t pooled_len(int64_t l) { return l < KW ? 0 : ((l - KW) / 2 + 1) / 2; }
 
@@ -134,8 +135,6 @@ __global__ __launch_bounds__(256) void zz_conv1_kernel(const float* __restrict__
 // Work-group: 4 waves = 2 M tiles (32 pooled outputs each) x 2 N tiles (32 output channels each).  Wave (mt, nt) keeps two
 // 32 x 32 accumulators (conv outputs 2p and 2p + 1) and walks K in groups of 8: per group one float4 of A per accumulator
 // and one float4 of B per lane, four MFMAs per accumulator.  The next group's operands are loaded before this group's MFMAs.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 __global__ __launch_bounds__(64 * CONV_WAVES) void zz_conv_kernel(const float* __restrict__ in, long long Lin, int cpad_in,
                                                                   long long M, long long Lp, int cout, int cpad_out,
                                                                   int n_tiles, const float4* __restrict__ frag,
@@ -269,17 +268,7 @@ extern "C" int stof_zonzini_pack_weights(const stof_zonzini_desc* desc, const fl
     for (int l = 1; l < g.layers; ++l) {                       // weight [cout][cin][10]
         const float* w = params[2 * l];
         const int cin = g.cout[l - 1], cp = g.cpad[l - 1], co = g.cout[l];
-        const int64_t groups = (int64_t)KW * cp / 8;
-        for (int nt = 0; nt < ntiles(co); ++nt)
-            for (int64_t q = 0; q < groups; ++q)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int s = 0; s < 4; ++s) {
-                        const int oc = 32 * nt + (lane & 31);
-                        const int64_t k = 8 * q + 4 * (lane >> 5) + s;
-                        const int tap = (int)(k / cp), ci = (int)(k % cp);
-                        const float v = (oc < co && ci < cin) ? w[((int64_t)oc * cin + ci) * KW + tap] : 0.f;
-                        blob[o.frag[l] + ((nt * groups + q) * 64 + lane) * 4 + s] = v;
-                    }
+        pack_frag32(w, co, cin, KW, cp, ntiles(co), (int64_t)KW * cp / 8, blob + o.frag[l]);
         for (int c = 0; c < co; ++c) blob[o.bias[l] + c] = params[2 * l + 1][c];
     }
     const int C = g.cout[g.layers - 1];

@@ -24,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .baselines import _KernelRoute, _pack
+from ._kernel_route import _KernelRoute, _pack
 
 MIN_INPUT_LENGTH = 641
 N_FILTERS = (128, 256, 512, 512)
@@ -66,6 +66,7 @@ class Kuleshov(_KernelRoute, nn.Module):
     128 -> 2 convolution whose flattened output feeds Linear(fc_dim, output_length)."""
     max_workspace_bytes = 512 << 20
     _KERNEL_CONFIG = 'rows of at least input_length samples with one eps in every BatchNorm'
+    _EVAL_ONLY = True
     tile_variant = 0            # 0: wave tile chosen per layer; 1, 2, 3 pin it (bitwise the same; for tests and timing)
 
     def __init__(self, input_length=None, output_length=None, num_layers=4):
@@ -101,15 +102,12 @@ class Kuleshov(_KernelRoute, nn.Module):
         self.final_conv = nn.Conv1d(nf[0], 2, 9)
         self.fc_dim = chain_lengths(self.input_length)['fc_dim']
         self.output_fc = nn.Linear(self.fc_dim, self.output_length)
-        self._packed = None
-        self._packed_key = None
 
     def _batch_norms(self):
         return [getattr(self, f'{p}_bn{i}') for p in ('down', 'up') for i in range(4)]
 
-    def _kernel_params(self):
-        # parameters and the BatchNorm running statistics, in the order the packer reads them
-        return [v for k, v in self.state_dict(keep_vars=True).items() if not k.endswith('num_batches_tracked')]
+    # parameters and the BatchNorm running statistics, in the order the packer reads them
+    _kernel_params = _KernelRoute._state_arrays
 
     def _config_supported(self):
         return len({float(bn.eps) for bn in self._batch_norms()}) == 1
@@ -125,15 +123,8 @@ class Kuleshov(_KernelRoute, nn.Module):
     def _pack(self, host):
         return pack_kuleshov_weights(self.input_length, self.output_length, host, self.down_bn0.eps)
 
-    def packed_weights(self, device):
-        eps = float(self.down_bn0.eps)
-        if getattr(self, '_packed_eps', None) != eps:
-            self.invalidate_packed()
-            self._packed_eps = eps
-        return super().packed_weights(device)
-
-    def forward(self, x):
-        return self.forward_kernels(x) if (not self.training and self._takes_kernels(x)) else self.forward_aten(x)
+    def _pack_key(self):
+        return (float(self.down_bn0.eps),)
 
     def forward_kernels(self, x):
         """y [N, 1, output_length] float32 on the gfx950 kernels with the running statistics (no autograd graph);
@@ -165,19 +156,15 @@ class Kuleshov(_KernelRoute, nn.Module):
         packed = self.packed_weights(x.device)
         lib = _lib.lib()
         desc = self._desc()
-        per_row = int(lib.stof_kuleshov_workspace_bytes(ctypes.byref(desc), 1))
-        chunk = max(1, min(N, int(self.max_workspace_bytes) // per_row))
-        ws_bytes = int(lib.stof_kuleshov_workspace_bytes(ctypes.byref(desc), chunk))
-        with torch.cuda.device(x.device):
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-            stream = _lib.stream_ptr(x.device)
-            for r0 in range(0, N, chunk):
-                rows = min(chunk, N - r0)
-                _lib.check(lib.stof_kuleshov_forward(
-                    ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), rows, row_stride, _lib.ptr(packed),
-                    ctypes.c_void_p(y[r0].data_ptr()), *[None if t is None else ctypes.c_void_p(t[r0].data_ptr())
-                                                         for t in (bott, fin_in, fin)],
-                    _lib.ptr(ws), ws_bytes, stream), 'stof_kuleshov_forward')
+
+        def launch(r0, rows, ws, ws_bytes, stream):
+            _lib.check(lib.stof_kuleshov_forward(
+                ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), rows, row_stride, _lib.ptr(packed),
+                ctypes.c_void_p(y[r0].data_ptr()), *[None if t is None else ctypes.c_void_p(t[r0].data_ptr())
+                                                     for t in (bott, fin_in, fin)],
+                _lib.ptr(ws), ws_bytes, stream), 'stof_kuleshov_forward')
+
+        self._chunked(x.device, N, lambda rows: int(lib.stof_kuleshov_workspace_bytes(ctypes.byref(desc), rows)), launch)
         return y, bott, fin_in, fin
 
     def forward_aten(self, x):

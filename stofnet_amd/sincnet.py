@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._kernel_route import _PackedKernels, _pack
 
 N_FILT = 128
 SINC_TAPS = 1023
@@ -120,11 +121,12 @@ class SincConv(nn.Module):
         return filter_bank(self.sample_rate, self.low_hz_.detach().cpu().numpy(), self.band_hz_.detach().cpu().numpy())
 
 
-class SincNet(nn.Module):
+class SincNet(_PackedKernels, nn.Module):
     """models/sincnet.py SincNet(options) for the option dict of main.py:145-157: sinc conv 1 -> 128 (1023 taps), Conv1d
     128 -> 128 (k 11), 128 -> 128 (k 9), 128 -> 1 (k 7), each "same" zero padded, followed by BatchNorm1d (eval) and
     LeakyReLU(0.2) (the last one linear).  x [N, L] or [N, 1, L] float32 -> y [N, 1, L]."""
     max_workspace_bytes = 512 << 20
+    _PACKED_ARRAYS = 'parameters and BatchNorm statistics'
 
     def __init__(self, options=None):
         super().__init__()
@@ -158,8 +160,6 @@ class SincNet(nn.Module):
                 self.conv.append(nn.Conv1d(self.cnn_N_filt[i - 1], self.cnn_N_filt[i], self.cnn_len_filt[i]))
             cur = int((cur - self.cnn_len_filt[i] + 1) / self.cnn_max_pool_len[i])
         self.out_dim = cur * self.cnn_N_filt[-1]
-        self._packed = None
-        self._packed_key = None
 
     def _desc(self, stop_after=0):
         eps = {float(b.eps) for b in self.bn}
@@ -167,7 +167,7 @@ class SincNet(nn.Module):
             raise NotImplementedError('SincNet: the BatchNorm layers must share one eps on the gfx950 path')
         return _lib.SincNetDesc(float(self.fs), eps.pop(), int(stop_after), 0)
 
-    def _params(self):
+    def _kernel_params(self):
         ps = [self.conv[0].low_hz_, self.conv[0].band_hz_]
         for conv in self.conv[1:]:
             ps += [conv.weight, conv.bias]
@@ -175,24 +175,13 @@ class SincNet(nn.Module):
             ps += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
         return ps
 
-    def invalidate_packed(self):
-        """Drop the packed weights (they are rebuilt on the next forward; parameter edits are also detected on their own)."""
-        self._packed = None
-        self._packed_key = None
-
-    def packed_weights(self, device):
-        params = self._params()
-        for p in params:
-            if p.dtype != torch.float32:
-                raise TypeError(f'SincNet: parameters and BatchNorm statistics must be float32 (got {p.dtype}); the '
-                                'gfx950 kernels are fp32 only')
+    def _pack_key(self):
         desc = self._desc()
-        key = (str(device), desc.fs, desc.bn_eps) + tuple((p.data_ptr(), p._version) for p in params)
-        if self._packed is None or self._packed_key != key:
-            host = [np.ascontiguousarray(p.detach().cpu().numpy(), dtype=np.float32) for p in params]
-            self._packed = pack_weights(desc.fs, host, desc.bn_eps).to(device)
-            self._packed_key = key
-        return self._packed
+        return (desc.fs, desc.bn_eps)
+
+    def _pack(self, host):
+        fs, bn_eps = self._pack_key()
+        return pack_weights(fs, host, bn_eps)
 
     def _check_input(self, x):
         if self.training:
@@ -236,17 +225,15 @@ class SincNet(nn.Module):
         packed = self.packed_weights(x.device)
         lib = _lib.lib()
         desc = self._desc(stop_after)
-        per_row = int(lib.stof_sincnet_workspace_bytes(ctypes.byref(desc), 1, L))
-        chunk = max(1, min(N, int(self.max_workspace_bytes) // per_row)) if chunked else N
-        ws_bytes = int(lib.stof_sincnet_workspace_bytes(ctypes.byref(desc), chunk, L))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        stream = _lib.stream_ptr(x.device)
-        for r0 in range(0, N, chunk):
-            n = min(chunk, N - r0)
+
+        def launch(r0, n, ws, ws_bytes, stream):
             _lib.check(lib.stof_sincnet_forward(
                 ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), n, L, _lib.ptr(packed),
                 None if y is None else ctypes.c_void_p(y[r0].data_ptr()), _lib.ptr(ws), ws_bytes, stream),
                 'stof_sincnet_forward')
+
+        ws, ws_bytes = self._chunked(x.device, N, lambda n: int(lib.stof_sincnet_workspace_bytes(ctypes.byref(desc), n, L)),
+                                     launch, chunked)
         return ws, ws_bytes // 2
 
 
@@ -255,14 +242,9 @@ def pack_weights(fs, params, bn_eps=1e-5):
     uint8 CPU tensor holding the blob."""
     lib = _lib.lib()
     desc = _lib.SincNetDesc(float(fs), float(bn_eps), 0, 0)
-    n = int(lib.stof_sincnet_packed_bytes(ctypes.byref(desc)))
-    if n == 0:
+    if not lib.stof_sincnet_packed_bytes(ctypes.byref(desc)):                # the description first, then the count, as ever
         raise ValueError(f'bad SincNet description (fs={fs!r}, bn_eps={bn_eps!r})')
     arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in params]
     if len(arrs) != 24:
         raise ValueError(f'SincNet packing needs 24 arrays, got {len(arrs)}')
-    ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    blob = torch.zeros(n, dtype=torch.uint8)
-    _lib.check(lib.stof_sincnet_pack_weights(ctypes.byref(desc), ptrs, ctypes.c_void_p(blob.data_ptr()), n),
-               'stof_sincnet_pack_weights')
-    return blob
+    return _pack(lib.stof_sincnet_packed_bytes, lib.stof_sincnet_pack_weights, desc, arrs, 'stof_sincnet_pack_weights')

@@ -22,7 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .baselines import _KernelRoute, _pack
+from ._kernel_route import _KernelRoute, _pack
 
 MAX_LAYERS = 12
 
@@ -57,6 +57,7 @@ class WaveUnet(_KernelRoute, nn.Module):
     output convolution on (decoder output, input) with tanh."""
     max_workspace_bytes = 512 << 20
     _KERNEL_CONFIG = 'a length that is a multiple of 2^n_layers'
+    _EVAL_ONLY = True
 
     def __init__(self, n_layers=12, channels_interval=24):
         super().__init__()
@@ -74,15 +75,9 @@ class WaveUnet(_KernelRoute, nn.Module):
         self.decoder = nn.ModuleList([_ConvBlock(2 * c * n if i == 0 else c * (2 * (n - i) + 1), c * (n - i), 5, 2)
                                       for i in range(n)])
         self.out = nn.Sequential(nn.Conv1d(1 + c, 1, kernel_size=1, stride=1), nn.Tanh())
-        self._packed = None
-        self._packed_key = None
 
-    def _kernel_params(self):
-        # parameters and the BatchNorm running statistics, in the order the packer reads them
-        return [v for k, v in self.state_dict(keep_vars=True).items() if not k.endswith('num_batches_tracked')]
-
-    def _config_supported(self):
-        return True
+    # parameters and the BatchNorm running statistics, in the order the packer reads them
+    _kernel_params = _KernelRoute._state_arrays
 
     def kernels_supported(self, x):
         """True when `forward_kernels(x)` can run: x float32 [N, 1, L] on the ROCm device with L a multiple of
@@ -91,9 +86,6 @@ class WaveUnet(_KernelRoute, nn.Module):
 
     def _pack(self, host):
         return pack_waveunet_weights(self.n_layers, host)
-
-    def forward(self, x):
-        return self.forward_kernels(x) if (not self.training and self._takes_kernels(x)) else self.forward_aten(x)
 
     def forward_kernels(self, x):
         """y [N, 1, L] float32 on the gfx950 kernels with the running statistics (no autograd graph); raises where they
@@ -119,19 +111,15 @@ class WaveUnet(_KernelRoute, nn.Module):
         packed = self.packed_weights(x.device)
         lib = _lib.lib()
         desc = _lib.WaveUnetDesc(n, 16)
-        per_row = int(lib.stof_waveunet_workspace_bytes(ctypes.byref(desc), 1, L))
-        chunk = max(1, min(N, int(self.max_workspace_bytes) // per_row))
-        ws_bytes = int(lib.stof_waveunet_workspace_bytes(ctypes.byref(desc), chunk, L))
-        with torch.cuda.device(x.device):
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-            stream = _lib.stream_ptr(x.device)
-            for r0 in range(0, N, chunk):
-                rows = min(chunk, N - r0)
-                _lib.check(lib.stof_waveunet_forward(
-                    ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), rows, L, _lib.ptr(packed),
-                    ctypes.c_void_p(y[r0].data_ptr()), None if bott is None else ctypes.c_void_p(bott[r0].data_ptr()),
-                    None if logits is None else ctypes.c_void_p(logits[r0].data_ptr()), _lib.ptr(ws), ws_bytes, stream),
-                    'stof_waveunet_forward')
+
+        def launch(r0, rows, ws, ws_bytes, stream):
+            _lib.check(lib.stof_waveunet_forward(
+                ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), rows, L, _lib.ptr(packed),
+                ctypes.c_void_p(y[r0].data_ptr()), None if bott is None else ctypes.c_void_p(bott[r0].data_ptr()),
+                None if logits is None else ctypes.c_void_p(logits[r0].data_ptr()), _lib.ptr(ws), ws_bytes, stream),
+                'stof_waveunet_forward')
+
+        self._chunked(x.device, N, lambda rows: int(lib.stof_waveunet_workspace_bytes(ctypes.byref(desc), rows, L)), launch)
         return y, bott, logits
 
     def forward_aten(self, x):

@@ -11,14 +11,14 @@ from __future__ import annotations
 
 import ctypes
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._kernel_route import _PackedKernels, _pack
 
 
-class _ZonziniNet(nn.Module):
+class _ZonziniNet(_PackedKernels, nn.Module):
     VARIANT = None
     CHANNELS = ()
     MIN_LEN = 0
@@ -37,35 +37,18 @@ class _ZonziniNet(nn.Module):
         self.global_avgpool = nn.AdaptiveAvgPool1d(1)
         self.fc1 = nn.Linear(cin, 1024)
         self.fc2 = nn.Linear(1024, 1)
-        self._packed = None
-        self._packed_key = None
 
     def _desc(self):
         return _lib.ZonziniDesc(self.VARIANT, 0)
 
-    def _params(self):
+    def _kernel_params(self):
         ps = []
         for conv in self.conv_layers:
             ps += [conv.weight, conv.bias]
         return ps + [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias]
 
-    def invalidate_packed(self):
-        """Drop the packed weights (they are rebuilt on the next forward; parameter edits are also detected on their own)."""
-        self._packed = None
-        self._packed_key = None
-
-    def packed_weights(self, device):
-        params = self._params()
-        for p in params:
-            if p.dtype != torch.float32:
-                raise TypeError(f'{type(self).__name__}: parameters must be float32 (got {p.dtype}); the gfx950 kernels '
-                                'are fp32 only')
-        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in params)
-        if self._packed is None or self._packed_key != key:
-            host = [np.ascontiguousarray(p.detach().cpu().numpy(), dtype=np.float32) for p in params]
-            self._packed = pack_weights(self.VARIANT, host).to(device)
-            self._packed_key = key
-        return self._packed
+    def _pack(self, host):
+        return pack_weights(self.VARIANT, host)
 
     def _check_input(self, x):
         _lib.require_device(x, 'x')
@@ -100,17 +83,14 @@ class _ZonziniNet(nn.Module):
         packed = self.packed_weights(x.device)
         lib = _lib.lib()
         desc = self._desc()
-        per_row = int(lib.stof_zonzini_workspace_bytes(ctypes.byref(desc), 1, L))
-        chunk = max(1, min(N, int(self.max_workspace_bytes) // per_row))
-        ws_bytes = int(lib.stof_zonzini_workspace_bytes(ctypes.byref(desc), chunk, L))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        stream = _lib.stream_ptr(x.device)
-        for r0 in range(0, N, chunk):
-            n = min(chunk, N - r0)
+
+        def launch(r0, n, ws, ws_bytes, stream):
             _lib.check(lib.stof_zonzini_forward(
                 ctypes.byref(desc), ctypes.c_void_p(x[r0].data_ptr()), n, L, _lib.ptr(packed),
                 ctypes.c_void_p(y[r0].data_ptr()), None if feats is None else ctypes.c_void_p(feats[r0].data_ptr()),
                 _lib.ptr(ws), ws_bytes, stream), 'stof_zonzini_forward')
+
+        self._chunked(x.device, N, lambda n: int(lib.stof_zonzini_workspace_bytes(ctypes.byref(desc), n, L)), launch)
         return y, feats
 
 
@@ -134,13 +114,5 @@ def pack_weights(variant, params):
     """Host-side packing (stof_zonzini_pack_weights) of the state_dict's float32 arrays in module order -> a uint8 CPU
     tensor holding the blob."""
     lib = _lib.lib()
-    desc = _lib.ZonziniDesc(int(variant), 0)
-    n = int(lib.stof_zonzini_packed_bytes(ctypes.byref(desc)))
-    if n == 0:
-        raise ValueError(f'unknown Zonzini variant {variant}')
-    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in params]
-    ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-    blob = torch.zeros(n, dtype=torch.uint8)
-    _lib.check(lib.stof_zonzini_pack_weights(ctypes.byref(desc), ptrs, ctypes.c_void_p(blob.data_ptr()), n),
-               'stof_zonzini_pack_weights')
-    return blob
+    return _pack(lib.stof_zonzini_packed_bytes, lib.stof_zonzini_pack_weights, _lib.ZonziniDesc(int(variant), 0), params,
+                 'stof_zonzini_pack_weights', f'unknown Zonzini variant {variant}')
