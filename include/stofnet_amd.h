@@ -551,6 +551,33 @@ int stof_train_conv1_c_wgrad(const float* x, const float* g, const float* saved,
                              void* stream);
 int stof_train_conv1_c_dgrad(const float* g, const float* saved, const float* w, float* dx, int64_t N, int32_t Cin,
                              int64_t L, int32_t F, float out_scale, void* stream);
+/* The two ends of EDSR_1D(1, 64, B, r | 64) (models/edsr_1d.py:22-45) for training; the 2 B + 1 body convolutions 64 -> 64,
+ * k 3 are stof_train_conv / stof_train_wgrad.  Exact fp32 on the vector pipe, activations channel-last [N][L][64], x / dx
+ * [N][L], y / dy [N][L r]: read channel-last, the trunk [N][L][64] IS its SampleShuffle1D(r) image [N][L r][64 / r].
+ * r in {1, 2, 4, 8, 16, 32, 64}.  Every [N][L][64] operand (a0, g, g2, saved, trunk, dtrunk) must be 16-byte aligned: all
+ * six kernels, stof_train_edsr_out included, move them as 16-byte vectors.
+ *   stof_train_edsr_in         a0 = relu(conv_input(x)), w (64,1,3), padding 1: one fmaf chain per output (bias, taps 0..2)
+ *   stof_train_edsr_in_wgrad   dw (64,1,3), db (64) = out_scale * gradient from (g + g2) * [saved > 0]; g2 (may be NULL) carries
+ *                              the long skip's gradient, saved = a0
+ *   stof_train_edsr_in_dgrad   dx = out_scale * conv_input^T((g + g2) * [saved > 0])
+ *   stof_train_edsr_out        y = conv_output(shuffle(trunk)), w (1,64/r,3): bias, then taps 0..2 over the channels in order
+ *   stof_train_edsr_out_dgrad  dtrunk[n][t][j (64/r) + c] = sum_k w[c][k] dy[n][t r + j - k + 1] (zero outside the waveform)
+ *   stof_train_edsr_out_wgrad  dw[c][k] = out_scale * sum dy[n][m] shuffle(trunk)[n][m + k - 1][c], db = out_scale * sum dy
+ * The weight gradients add per-group partials from `workspace` (the *_workspace_bytes query) in a fixed order: no float
+ * atomics, two runs are bitwise equal.  STOF_ERR_BAD_ARG on NULL or a bad r, STOF_OK on an empty batch (dw / db zeroed),
+ * STOF_ERR_UNSUPPORTED where N L 64 reaches 2^31.                                                                        */
+int stof_train_edsr_in(const float* x, const float* w, const float* b, float* y, int64_t N, int64_t L, void* stream);
+size_t stof_train_edsr_in_wgrad_workspace_bytes(void);
+int stof_train_edsr_in_wgrad(const float* x, const float* g, const float* g2, const float* saved, float* dw, float* db,
+                             int64_t N, int64_t L, float out_scale, void* workspace, size_t workspace_bytes, void* stream);
+int stof_train_edsr_in_dgrad(const float* g, const float* g2, const float* saved, const float* w, float* dx, int64_t N,
+                             int64_t L, float out_scale, void* stream);
+int stof_train_edsr_out(const float* trunk, const float* w, const float* b, float* y, int64_t N, int64_t L, int32_t r,
+                        void* stream);
+int stof_train_edsr_out_dgrad(const float* dy, const float* w, float* dtrunk, int64_t N, int64_t L, int32_t r, void* stream);
+size_t stof_train_edsr_out_wgrad_workspace_bytes(int32_t r);
+int stof_train_edsr_out_wgrad(const float* trunk, const float* dy, float* dw, float* db, int64_t N, int64_t L, int32_t r,
+                              float out_scale, void* workspace, size_t workspace_bytes, void* stream);
 /* SemiGlobalBlock pieces (models/stofnet.py:103,108-115), channel-last: MaxPool1d(scale, scale) with arg-max
  * (scale = sample_scale <= 256, P = floor(L / scale) windows), its routing backward (times lrelu' of the pre-pool
  * activation), nearest upsample x scale + pad (rem_half = (L - P*scale) / 2 on each side) + add and its backward.

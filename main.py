@@ -8,7 +8,9 @@ load_state_dict (main.py:173-177), the eval loop's `model(frame)` -> `mask2coord
 `toa_rmse` sequence (main.py:314,320,347), and with `evaluate=False` the training loop
 (main.py:199-289: Gaussian-mask loss, AdamW, CosineAnnealingLR per epoch, EarlyStopping on the
 summed validation loss, checkpoint `<run_name>_rf-scale<rf>_epoch_<e>.pth`, main.py:423-426) on the
-HIP training kernels; launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
+HIP training kernels, for model=stofnet and model=edsr (EDSR_1D: torch loss and optimizer on the module's autograd
+boundary, exact fp32; `train_route=kernels` runs the backward pass on the gfx950 kernels, `train_route=aten` on stock ATen
+layers; every other model evaluates only); launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
 one flat gradient all-reduce per step over RCCL).  `augment=True` puts the reference's training transforms in front of every
 training step (main.py:49,54,82: CropChannelData(crop_ratio) + AddNoise(snr_db) on chirp data, AddNoise alone otherwise) as
 one launch of the device kernel (stofnet_amd/augment.py); `shuffle=True` reorders the training rows every epoch
@@ -107,8 +109,7 @@ def main(argv=None):
     if name == 'stofnet':
         model = StofNet(upsample_factor=cfg.upsample_factor, precision=cfg.precision)
     elif name == 'edsr':                                                  # main.py:139-142: baselines riding on SampleShuffle1D
-        model = EDSR_1D(num_channels=1, num_features=64, num_blocks=8, upscale_factor=cfg.upsample_factor)
-        cfg.evaluate = True
+        model = EDSR_1D(num_channels=1, num_features=64, num_blocks=8, upscale_factor=cfg.upsample_factor)   # trains: train()
     elif name == 'espcn':
         model = ESPCN_1D(upscale_factor=cfg.upsample_factor)
         cfg.evaluate = True
@@ -163,13 +164,15 @@ def main(argv=None):
     log = RunLog(cfg)
     if log.enabled and str(cfg.run_name) == 'local-run':
         cfg.run_name = log.name                                          # the reference names checkpoints after the wandb run
-    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name == 'stofnet') else None
+    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name in ('stofnet', 'edsr')) else None
     es_all, summary = evaluate(model, name, frames, gt, cfg, log)
     log.summary({'model_name': name, 'total_parameters': int(sum(p.numel() for p in model.parameters())),
                  'total_jaccard': summary.get('total_jaccard'), 'total_inference_time': summary['inference_time'],
                  'total_distance_mean': summary.get('total_distance_mean'), 'total_distance_std': summary.get('total_distance_std')})
     if history is not None:
         summary['train_history'] = history
+        if name == 'edsr':
+            summary['train_route'], summary['train_precision'] = model.train_route, 'fp32'
     if int(os.environ.get('RANK', '0')) == 0:
         print(json.dumps(summary))
     return es_all, summary
@@ -190,6 +193,11 @@ def epoch_batches(n_rows, bs, epoch, rank, world, shuffle=False, seed=0):
 def train(model, frames, gt, cfg, log=None):
     """main.py:199-289 + 403-410 + 423-426 on the HIP training kernels (stofnet_amd/training.py).
 
+    StofNet trains through `StofNetTrainer` or, with trainer=autograd, through the reference's own torch lines on the module's
+    autograd boundary.  EDSR_1D (model=edsr) always takes those torch lines, in exact fp32 whatever `train_precision` says:
+    with train_route=kernels `loss.backward()` runs the gfx950 kernels (stofnet_amd/edsr_training.py), with train_route=aten
+    the same loop runs on stock ATen layers.
+
     With `augment=True` every training batch goes through stofnet_amd.augment.Augment first (generator: seed = cfg.seed,
     rank = RANK, one `call` per step) and the ground truth moves with the crop window before it becomes sample indices.
     The held-out validation tail is NOT augmented.  This differs from the reference on purpose: there the validation split
@@ -203,9 +211,10 @@ def train(model, frames, gt, cfg, log=None):
     rank = int(os.environ.get('RANK', '0'))
     if world > 1 and not dist.is_initialized():
         dist.init_process_group('nccl', device_id=torch.device(cfg.device))
-    tr = StofNetTrainer(model, lr=cfg.lr, weight_decay=cfg.weight_decay, lambda_value=cfg.lambda_value,
-                        mask_amplitude=cfg.mask_amplitude, kernel_size=cfg.kernel_size, sigma=cfg.sigma,
-                        precision=cfg.train_precision)
+    edsr = isinstance(model, EDSR_1D)
+    tr = None if edsr else StofNetTrainer(model, lr=cfg.lr, weight_decay=cfg.weight_decay, lambda_value=cfg.lambda_value,
+                                          mask_amplitude=cfg.mask_amplitude, kernel_size=cfg.kernel_size, sigma=cfg.sigma,
+                                          precision=cfg.train_precision)
     r, bs = int(cfg.upsample_factor), int(cfg.batch_size)
     n_val = max(bs, int(frames.shape[0] * 0.1) // bs * bs)              # held-out tail for early stopping
     tr_x, tr_gt = frames[:-n_val], gt[:-n_val]
@@ -227,28 +236,38 @@ def train(model, frames, gt, cfg, log=None):
         g = torch.where(g <= 0, torch.zeros_like(g), g)                  # main.py:217
         return torch.round(g.unsqueeze(1) * r).long()                    # main.py:218
 
-    autograd = str(getattr(cfg, 'trainer', 'fused')) == 'autograd'
+    autograd = edsr or str(getattr(cfg, 'trainer', 'fused')) == 'autograd'
     if autograd:
         # the reference's own training lines (main.py:179-180,184-188,221-248,288) on the module's autograd boundary:
         # torch loss, torch.optim.AdamW, CosineAnnealingLR; `loss.backward()` runs the stof_train_* kernels
         import torch.nn.functional as F
         from stofnet_amd.mask2samples import coords2mask
         from stofnet_amd.training import allreduce_max_, allreduce_mean_, gaussian_kernel
-        model.train_precision = str(cfg.train_precision)
+        if edsr:
+            route = str(getattr(cfg, 'train_route', 'kernels'))
+            if route not in ('kernels', 'aten'):
+                raise ValueError(f"train_route must be 'kernels' or 'aten' (got {route!r})")
+            model.train_route = route
+        else:
+            model.train_precision = str(cfg.train_precision)
         optimizer = torch.optim.AdamW(model.parameters(), lr=float(cfg.lr), weight_decay=float(cfg.weight_decay))
         scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, int(cfg.epochs))
         loss_mse, loss_l1 = torch.nn.MSELoss(reduction='mean'), torch.nn.L1Loss(reduction='mean')
         gauss = torch.tensor(gaussian_kernel(int(cfg.kernel_size), cfg.sigma), dtype=torch.float32,
                              device=cfg.device).unsqueeze(0).unsqueeze(0)
 
-        def autograd_step(frame, gt_true):
-            masks_pred = model(frame)                                                            # main.py:221
+        def torch_loss(masks_pred, gt_true, sharded=True):
             masks_true = coords2mask(gt_true, masks_pred)                                        # main.py:228
             blur = F.conv1d(masks_true, gauss, padding=int(cfg.kernel_size) // 2)                # main.py:229
-            blur = blur / allreduce_max_(blur.max().reshape(1))                                  # main.py:230 (whole batch, all ranks)
+            bmax = blur.max().reshape(1)
+            blur = blur / (allreduce_max_(bmax) if sharded else bmax)                            # main.py:230 (whole batch, all ranks)
             blur = blur * float(cfg.mask_amplitude)                                              # main.py:231
-            loss = (loss_mse(masks_pred.squeeze(1), blur.squeeze(1).float()) +
+            return (loss_mse(masks_pred.squeeze(1), blur.squeeze(1).float()) +
                     loss_l1(masks_pred.squeeze(1), torch.zeros_like(masks_pred.squeeze(1))) * float(cfg.lambda_value))   # main.py:232
+
+        def autograd_step(frame, gt_true):
+            masks_pred = model(frame)                                                            # main.py:221
+            loss = torch_loss(masks_pred, gt_true)
             optimizer.zero_grad()                                                                # main.py:246
             loss.backward()                                                                      # main.py:247
             if world > 1:                                                                        # DDP: mean of the shard gradients
@@ -257,6 +276,8 @@ def train(model, frames, gt, cfg, log=None):
             optimizer.step()                                                                     # main.py:248
             return loss.detach(), masks_pred.detach()
 
+    # validation loss (main.py:322-326): the loss kernels of the trainer, or the same torch lines where there is none
+    val_loss = tr.loss if tr is not None else (lambda pred, g: torch_loss(pred, g, sharded=False))
     for e in range(int(cfg.epochs)):
         if not autograd:
             tr.set_lr_cosine(e, int(cfg.epochs), float(cfg.lr))          # CosineAnnealingLR stepped per epoch
@@ -279,7 +300,7 @@ def train(model, frames, gt, cfg, log=None):
         with torch.no_grad():
             for b0 in range(0, va_x.shape[0] - bs + 1, bs):
                 pred = model(torch.from_numpy(va_x[b0:b0 + bs]).to(cfg.device))
-                val += float(tr.loss(pred, gt_true_of(va_gt[b0:b0 + bs])))
+                val += float(val_loss(pred, gt_true_of(va_gt[b0:b0 + bs])))
         lr_now = optimizer.param_groups[0]['lr'] if autograd else tr.lr
         if autograd:
             scheduler.step()                                                                                # main.py:288

@@ -14,7 +14,14 @@ reference.  Each network has two routes:
 torch.no_grad(), or when neither x nor any parameter requires grad); everything else (CPU tensors, other dtypes,
 other widths, training) stays on `forward_aten`.  Packed weights are cached per (device, storage, `_version`) of every
 parameter, so parameter edits are picked up on their own; rows are bitwise independent of their batch, so EDSR's
-chunking under `max_workspace_bytes` does not show in the result."""
+chunking under `max_workspace_bytes` does not show in the result.
+
+EDSR_1D has a third route, opt-in with `train_route = 'kernels'`:
+
+  forward_train_kernels(x)  the same network behind an autograd boundary (edsr_training.py): `loss.backward()` runs the
+                            gfx950 training kernels in exact fp32, deterministic and free of MIOpen.
+
+With it `forward` takes the training kernels wherever it took `forward_aten` only because a graph is recorded."""
 import ctypes
 
 import torch
@@ -23,6 +30,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._kernel_route import _KernelRoute, _pack
+from .edsr_training import EdsrFunction, EdsrTrainEngine
 from .sample_shuffle import SampleShuffle1D
 
 
@@ -63,6 +71,7 @@ class EDSR_1D(_KernelRoute, nn.Module):
     """models/edsr_1d.py:22-45: input conv + ReLU, `num_blocks` residual blocks, mid conv with the long skip,
     SampleShuffle1D (C = num_features / upscale_factor channels survive), output conv."""
     max_workspace_bytes = 512 << 20
+    train_route = 'aten'            # 'aten' | 'kernels': which route `forward` takes when an autograd graph is recorded
     _KERNEL_CONFIG = 'num_channels = 1, num_features = 64 and an upscale_factor that divides 64'
 
     def __init__(self, num_channels=1, num_features=64, num_blocks=8, upscale_factor=4):
@@ -111,6 +120,26 @@ class EDSR_1D(_KernelRoute, nn.Module):
 
         self._chunked(x.device, N, lambda n: int(lib.stof_edsr_workspace_bytes(ctypes.byref(desc), n, L)), launch)
         return y, trunk
+
+    def forward_train_kernels(self, x):
+        """y [N, 1, L r] float32 on the gfx950 training kernels, with an autograd graph: its backward fills the gradient of
+        every parameter (and of x, if it asks for one) in exact fp32; raises where the kernels do not apply."""
+        self._check_kernels(x)
+        engines = self.__dict__.setdefault('_train_engines', {})
+        key = (str(x.device), len(self.residual_blocks), int(self.upscale.upsample_factor))
+        engine = engines.get(key)
+        if engine is None:
+            engine = engines[key] = EdsrTrainEngine(x.device, key[1], key[2])
+        names, params = zip(*self.named_parameters())
+        return EdsrFunction.apply(x, engine, names, *params)
+
+    def forward(self, x):
+        if self.train_route not in ('aten', 'kernels'):
+            raise ValueError(f"EDSR_1D.train_route must be 'aten' or 'kernels' (got {self.train_route!r})")
+        if (self.train_route == 'kernels' and self.kernels_supported(x) and torch.is_grad_enabled()
+                and (x.requires_grad or any(p.requires_grad for p in self._kernel_params()))):
+            return self.forward_train_kernels(x)
+        return super().forward(x)
 
     def forward_aten(self, x):
         first = self.relu(self.conv_input(x))

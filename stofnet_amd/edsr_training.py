@@ -1,0 +1,144 @@
+"""Training EDSR_1D(1, 64, B, r | 64) on the gfx950 kernels (reference main.py:199-289 with models/edsr_1d.py:22-45): forward with
+saved activations and the full backward pass in exact fp32 on channel-last [N][L][64] buffers, behind an autograd boundary.
+
+The 2 B + 1 body convolutions are `stof_train_conv` / `stof_train_wgrad` (csrc/train.hip, through `LayerKernels`); the two
+ends -- conv_input + ReLU and the shuffled conv_output, each with its weight and data gradient -- are the vector-pipe
+kernels of csrc/edsr_train.hip.  In channel-last order the trunk [N][L][64] read as [N][L r][64 / r] is its
+SampleShuffle1D(r) image, so the shuffle costs nothing in either direction.  No MIOpen call and no float atomic: two runs
+give bitwise equal gradients."""
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from .training import ACT_NONE, ACT_RELU, LayerKernels
+
+
+@dataclass
+class EdsrSaved:
+    """What one forward keeps for its backward."""
+    p: dict                 # name -> parameter tensor of this step
+    versions: dict          # name -> its `_version` in the forward: the backward reads the parameters again
+    x: torch.Tensor         # [N, L] input frame
+    a0: torch.Tensor        # [N, L, 64] relu(conv_input)
+    hs: list                # hs[i] = relu(conv1) of block i
+    us: list                # us[i] = input of block i (us[0] = a0), us[B] = conv_mid's input
+    trunk: torch.Tensor     # [N, L, 64] conv_mid + a0 = the input of `upscale`
+
+
+class EdsrTrainEngine(LayerKernels):
+    """Forward with saved activations and backward pass of EDSR_1D on explicit parameter / gradient dictionaries (the
+    state_dict's names), mirroring `TrainEngine`."""
+
+    def __init__(self, dev, num_blocks, r):
+        super().__init__(dev, _lib.PREC_FP32)
+        self.B, self.r = int(num_blocks), int(r)
+        self._images = {}           # (layer name, flip) -> ((data_ptr, _version) of the weight, its kernel-layout image)
+
+    def body_layers(self):
+        return [f'residual_blocks.{i}.conv{j}' for i in range(self.B) for j in (1, 2)] + ['conv_mid']
+
+    def _image(self, p, name, flip):
+        """Tap-major image of a 64 -> 64 weight (flip: the data-gradient operand), repacked when the parameter changed."""
+        w = p[name + '.weight']
+        key = (w.data_ptr(), w._version)
+        hit = self._images.get((name, flip))
+        if hit is None or hit[0] != key:
+            hit = self._images[(name, flip)] = (key, self._repack(w.contiguous(), flip))
+        return hit[1]
+
+    def _forward_saved(self, p, frame):
+        """models/edsr_1d.py:38-45 -> (y [N, L r], EdsrSaved)."""
+        _lib.require_device(frame, 'frame')
+        lib, st = _lib.lib(), self._st()
+        x = frame.detach().reshape(frame.shape[0], frame.shape[-1]).contiguous().float()
+        n, L = x.shape
+        p = {k: v.contiguous() for k, v in p.items()}
+        fwd = {nm: self._image(p, nm, False) for nm in self.body_layers()}
+        a0 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
+        _lib.check(lib.stof_train_edsr_in(_lib.ptr(x), _lib.ptr(p['conv_input.weight']), _lib.ptr(p['conv_input.bias']), _lib.ptr(a0),
+                                          n, L, st), 'stof_train_edsr_in')
+        u, hs, us = a0, [], [a0]
+        for i in range(self.B):
+            c1, c2 = f'residual_blocks.{i}.conv1', f'residual_blocks.{i}.conv2'
+            h = self._conv(u, fwd[c1], p[c1 + '.bias'], 64, 64, 3, ACT_RELU)
+            u = self._conv(h, fwd[c2], p[c2 + '.bias'], 64, 64, 3, ACT_NONE, residual=u)
+            hs.append(h)
+            us.append(u)
+        trunk = self._conv(u, fwd['conv_mid'], p['conv_mid.bias'], 64, 64, 3, ACT_NONE, residual=a0)
+        y = torch.empty((n, L * self.r), dtype=torch.float32, device=self.dev)
+        _lib.check(lib.stof_train_edsr_out(_lib.ptr(trunk), _lib.ptr(p['conv_output.weight']), _lib.ptr(p['conv_output.bias']),
+                                           _lib.ptr(y), n, L, self.r, st), 'stof_train_edsr_out')
+        return y, EdsrSaved(p=p, versions={k: v._version for k, v in p.items()}, x=x, a0=a0, hs=hs, us=us, trunk=trunk)
+
+    def _backward_saved(self, saved, dy, g, dx=None):
+        """From dy [N, L r] = dloss/dy: every parameter gradient into the tensors of `g` (name -> tensor of the parameter's
+        shape) and, if `dx` [N, L] is given, the gradient with respect to the input frame into it."""
+        lib, st, p, r = _lib.lib(), self._st(), saved.p, self.r
+        n, L = saved.x.shape
+        # the data gradients read the weights again (the flipped images are packed here, only when a backward runs): an
+        # in-place edit since the forward would be used silently, where torch's own convolutions raise
+        for k, v in p.items():
+            if v._version != saved.versions[k]:
+                raise RuntimeError(f'EDSR_1D: parameter {k} needed for gradient computation has been modified by an inplace '
+                                   f'operation (version {v._version}, expected {saved.versions[k]})')
+        bwd = {nm: self._image(p, nm, True) for nm in self.body_layers()}
+        ws = self._scratch('_edsr_out_ws', lib.stof_train_edsr_out_wgrad_workspace_bytes(r))
+        _lib.check(lib.stof_train_edsr_out_wgrad(_lib.ptr(saved.trunk), _lib.ptr(dy), _lib.ptr(g['conv_output.weight']),
+                                                 _lib.ptr(g['conv_output.bias']), n, L, r, 1.0, _lib.ptr(ws), ws.numel(), st),
+                   'stof_train_edsr_out_wgrad')
+        gt = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)            # dloss/dtrunk: also the long skip's gradient
+        _lib.check(lib.stof_train_edsr_out_dgrad(_lib.ptr(dy), _lib.ptr(p['conv_output.weight']), _lib.ptr(gt), n, L, r, st),
+                   'stof_train_edsr_out_dgrad')
+        self._wgrad(saved.us[self.B], gt, g['conv_mid.weight'], g['conv_mid.bias'], 64, 64, 3)
+        gu = self._conv(gt, bwd['conv_mid'], None, 64, 64, 3)
+        for i in range(self.B - 1, -1, -1):                  # gu = dloss/d(output of block i), the identity path included
+            c1, c2 = f'residual_blocks.{i}.conv1', f'residual_blocks.{i}.conv2'
+            self._wgrad(saved.hs[i], gu, g[c2 + '.weight'], g[c2 + '.bias'], 64, 64, 3)
+            gh = self._conv(gu, bwd[c2], None, 64, 64, 3, ACT_RELU, saved=saved.hs[i])
+            self._wgrad(saved.us[i], gh, g[c1 + '.weight'], g[c1 + '.bias'], 64, 64, 3)
+            gu = self._conv(gh, bwd[c1], None, 64, 64, 3, residual=gu)
+        ws = self._scratch('_edsr_in_ws', lib.stof_train_edsr_in_wgrad_workspace_bytes())
+        _lib.check(lib.stof_train_edsr_in_wgrad(_lib.ptr(saved.x), _lib.ptr(gu), _lib.ptr(gt), _lib.ptr(saved.a0),
+                                                _lib.ptr(g['conv_input.weight']), _lib.ptr(g['conv_input.bias']), n, L, 1.0,
+                                                _lib.ptr(ws), ws.numel(), st), 'stof_train_edsr_in_wgrad')
+        if dx is not None:
+            _lib.check(lib.stof_train_edsr_in_dgrad(_lib.ptr(gu), _lib.ptr(gt), _lib.ptr(saved.a0), _lib.ptr(p['conv_input.weight']),
+                                                    _lib.ptr(dx), n, L, 1.0, st), 'stof_train_edsr_in_dgrad')
+
+
+class EdsrFunction(torch.autograd.Function):
+    """Autograd boundary of `EDSR_1D.forward_train_kernels`, on the pattern of `StofNetFunction`: `y = model(frame)` returns a
+    tensor whose `backward()` runs the gfx950 data- and weight-gradient kernels and hands torch the gradient of every
+    parameter (and of the frame, when it asks for one), so torch's loss, `optim.AdamW` and scheduler run unchanged."""
+
+    @staticmethod
+    def forward(ctx, frame, engine, names, *params):
+        n, L = int(frame.shape[0]), int(frame.shape[-1])
+        ctx.engine, ctx.names, ctx.shapes, ctx.dims = engine, names, [tuple(v.shape) for v in params], (n, L)
+        if n == 0 or L == 0:
+            ctx.saved = ()
+            return torch.empty((n, 1, L * engine.r), dtype=torch.float32, device=engine.dev)
+        with torch.cuda.device(engine.dev):
+            y, ctx.saved = engine._forward_saved({k: v.detach() for k, v in zip(names, params)}, frame)
+        return y.view(n, 1, L * engine.r)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        engine, saved, (n, L) = ctx.engine, ctx.saved, ctx.dims
+        if saved is None:
+            raise RuntimeError('Trying to backward through the graph a second time: the saved activations of '
+                               'EDSR_1D.forward have been freed')
+        with torch.cuda.device(engine.dev):
+            sizes = [int(np.prod(sh)) if len(sh) else 1 for sh in ctx.shapes]
+            flat = torch.zeros(sum(sizes), dtype=torch.float32, device=engine.dev)    # fresh: torch may keep these views as .grad
+            g, off = {}, 0
+            for name, sh, k in zip(ctx.names, ctx.shapes, sizes):
+                g[name] = flat[off:off + k].view(sh)
+                off += k
+            dx = torch.empty((n, L), dtype=torch.float32, device=engine.dev) if ctx.needs_input_grad[0] else None
+            if n and L:
+                engine._backward_saved(saved, grad_out.detach().reshape(n, L * engine.r).contiguous().float(), g, dx)
+        ctx.saved = None
+        return (None if dx is None else dx.view(n, 1, L), None, None) + tuple(g[name] for name in ctx.names)
