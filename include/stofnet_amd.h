@@ -578,6 +578,41 @@ int stof_train_edsr_out_dgrad(const float* dy, const float* w, float* dtrunk, in
 size_t stof_train_edsr_out_wgrad_workspace_bytes(int32_t r);
 int stof_train_edsr_out_wgrad(const float* trunk, const float* dy, float* dw, float* db, int64_t N, int64_t L, int32_t r,
                               float out_scale, void* workspace, size_t workspace_bytes, void* stream);
+/* ESPCN_1D(r) (models/espcn_1d.py:31-36), r = 1..64, for training: one entry per stage, exact fp32, activations saved in
+ * device memory channel-last and un-gapped: h1 [N][L][64], h2 [N][L][32], x / dx [N][L], y / dy [N][L r] (channel-last z
+ * [N][L][r] IS the shuffled row, so y[n][l r + j] = sigmoid(z[n][l][j])).  The zero padding of conv2 and conv3 is zeros of h1
+ * and h2.  h1, h2, g1, g2 and the fragment image must be 16-byte aligned (moved as 16-byte vectors); x, y, dy, dx and the
+ * parameters, read in torch layout from device memory, need 4 bytes.
+ *   stof_train_espcn_in         h1 = tanh(conv1(x)), w (64,1,5), padding 2: one fmaf chain per output (bias, taps 0..4)
+ *   stof_train_espcn_repack     conv2.weight (32,64,3) -> the stof_train_espcn_repack_floats() floats of the MFMA operand image
+ *                               that stof_train_espcn_mid reads (on the device; repack when the weight changes)
+ *   stof_train_espcn_mid        h2 = tanh(conv2(h1) + b2) on v_mfma_f32_32x32x2_f32: k = tap 64 + ci, K group q (8 products) into
+ *                               partial sum q mod 8, the eight sums added in order, then the bias
+ *   stof_train_espcn_out        y = sigmoid(conv3(h2) + b3), w (r,32,3): bias, then taps 0..2 over the channels in order
+ *   stof_train_espcn_out_wgrad  dw (r,32,3), db (r) = out_scale * gradient from dz = dy y (1 - y) and h2; y = the saved output
+ *   stof_train_espcn_out_dgrad  g2 [N][L][32] = conv3^T(dz) (1 - h2^2): tanh' of conv2's output is applied here, so conv2's two
+ *                               gradients are stof_train_wgrad(h1, g2, 64 -> 32) and stof_train_conv(g2, flipped image, 32 -> 64)
+ *   stof_train_espcn_in_wgrad   dw (64,1,5), db (64) = out_scale * gradient from g1 (1 - h1^2) and x
+ *   stof_train_espcn_in_dgrad   dx = out_scale * conv1^T(g1 (1 - h1^2))
+ * The weight gradients add per-group partials from `workspace` (the *_workspace_bytes query) in a fixed order: no float
+ * atomics, two runs are bitwise equal.  STOF_ERR_BAD_ARG on NULL or r outside 1..64, STOF_OK on an empty batch (dw / db
+ * zeroed), STOF_ERR_UNSUPPORTED where N L 64 reaches 2^31.                                                               */
+size_t stof_train_espcn_repack_floats(void);
+int stof_train_espcn_repack(const float* w2, float* out, void* stream);
+int stof_train_espcn_in(const float* x, const float* w, const float* b, float* h1, int64_t N, int64_t L, void* stream);
+int stof_train_espcn_mid(const float* h1, const float* frag2, const float* b2, float* h2, int64_t N, int64_t L, void* stream);
+int stof_train_espcn_out(const float* h2, const float* w, const float* b, float* y, int64_t N, int64_t L, int32_t r,
+                         void* stream);
+size_t stof_train_espcn_out_wgrad_workspace_bytes(int32_t r);
+int stof_train_espcn_out_wgrad(const float* h2, const float* y, const float* dy, float* dw, float* db, int64_t N, int64_t L,
+                               int32_t r, float out_scale, void* workspace, size_t workspace_bytes, void* stream);
+int stof_train_espcn_out_dgrad(const float* y, const float* dy, const float* h2, const float* w, float* g2, int64_t N,
+                               int64_t L, int32_t r, void* stream);
+size_t stof_train_espcn_in_wgrad_workspace_bytes(void);
+int stof_train_espcn_in_wgrad(const float* x, const float* g1, const float* h1, float* dw, float* db, int64_t N, int64_t L,
+                              float out_scale, void* workspace, size_t workspace_bytes, void* stream);
+int stof_train_espcn_in_dgrad(const float* g1, const float* h1, const float* w, float* dx, int64_t N, int64_t L,
+                              float out_scale, void* stream);
 /* SemiGlobalBlock pieces (models/stofnet.py:103,108-115), channel-last: MaxPool1d(scale, scale) with arg-max
  * (scale = sample_scale <= 256, P = floor(L / scale) windows), its routing backward (times lrelu' of the pre-pool
  * activation), nearest upsample x scale + pad (rem_half = (L - P*scale) / 2 on each side) + add and its backward.

@@ -8,8 +8,8 @@ load_state_dict (main.py:173-177), the eval loop's `model(frame)` -> `mask2coord
 `toa_rmse` sequence (main.py:314,320,347), and with `evaluate=False` the training loop
 (main.py:199-289: Gaussian-mask loss, AdamW, CosineAnnealingLR per epoch, EarlyStopping on the
 summed validation loss, checkpoint `<run_name>_rf-scale<rf>_epoch_<e>.pth`, main.py:423-426) on the
-HIP training kernels, for model=stofnet and model=edsr (EDSR_1D: torch loss and optimizer on the module's autograd
-boundary, exact fp32; `train_route=kernels` runs the backward pass on the gfx950 kernels, `train_route=aten` on stock ATen
+HIP training kernels, for model=stofnet, model=edsr and model=espcn (EDSR_1D, ESPCN_1D: torch loss and optimizer on the module's
+autograd boundary, exact fp32; `train_route=kernels` runs the backward pass on the gfx950 kernels, `train_route=aten` on stock ATen
 layers; every other model evaluates only); launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
 one flat gradient all-reduce per step over RCCL).  `augment=True` puts the reference's training transforms in front of every
 training step (main.py:49,54,82: CropChannelData(crop_ratio) + AddNoise(snr_db) on chirp data, AddNoise alone otherwise) as
@@ -111,8 +111,7 @@ def main(argv=None):
     elif name == 'edsr':                                                  # main.py:139-142: baselines riding on SampleShuffle1D
         model = EDSR_1D(num_channels=1, num_features=64, num_blocks=8, upscale_factor=cfg.upsample_factor)   # trains: train()
     elif name == 'espcn':
-        model = ESPCN_1D(upscale_factor=cfg.upsample_factor)
-        cfg.evaluate = True
+        model = ESPCN_1D(upscale_factor=cfg.upsample_factor)                  # trains: train()
     elif name == 'zonzini':                                               # main.py:135-136: Small on chirp data, else Large
         model = ZonziniNetSmall() if 'chirp' in str(cfg.data_dir).lower() else ZonziniNetLarge()
         cfg.evaluate = True                                               # inference only on the gfx950 path
@@ -164,14 +163,14 @@ def main(argv=None):
     log = RunLog(cfg)
     if log.enabled and str(cfg.run_name) == 'local-run':
         cfg.run_name = log.name                                          # the reference names checkpoints after the wandb run
-    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name in ('stofnet', 'edsr')) else None
+    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name in ('stofnet', 'edsr', 'espcn')) else None
     es_all, summary = evaluate(model, name, frames, gt, cfg, log)
     log.summary({'model_name': name, 'total_parameters': int(sum(p.numel() for p in model.parameters())),
                  'total_jaccard': summary.get('total_jaccard'), 'total_inference_time': summary['inference_time'],
                  'total_distance_mean': summary.get('total_distance_mean'), 'total_distance_std': summary.get('total_distance_std')})
     if history is not None:
         summary['train_history'] = history
-        if name == 'edsr':
+        if name in ('edsr', 'espcn'):
             summary['train_route'], summary['train_precision'] = model.train_route, 'fp32'
     if int(os.environ.get('RANK', '0')) == 0:
         print(json.dumps(summary))
@@ -194,9 +193,9 @@ def train(model, frames, gt, cfg, log=None):
     """main.py:199-289 + 403-410 + 423-426 on the HIP training kernels (stofnet_amd/training.py).
 
     StofNet trains through `StofNetTrainer` or, with trainer=autograd, through the reference's own torch lines on the module's
-    autograd boundary.  EDSR_1D (model=edsr) always takes those torch lines, in exact fp32 whatever `train_precision` says:
-    with train_route=kernels `loss.backward()` runs the gfx950 kernels (stofnet_amd/edsr_training.py), with train_route=aten
-    the same loop runs on stock ATen layers.
+    autograd boundary.  EDSR_1D (model=edsr) and ESPCN_1D (model=espcn) always take those torch lines, in exact fp32 whatever
+    `train_precision` says: with train_route=kernels `loss.backward()` runs the gfx950 kernels (stofnet_amd/edsr_training.py,
+    stofnet_amd/espcn_training.py), with train_route=aten the same loop runs on stock ATen layers.
 
     With `augment=True` every training batch goes through stofnet_amd.augment.Augment first (generator: seed = cfg.seed,
     rank = RANK, one `call` per step) and the ground truth moves with the crop window before it becomes sample indices.
@@ -211,10 +210,10 @@ def train(model, frames, gt, cfg, log=None):
     rank = int(os.environ.get('RANK', '0'))
     if world > 1 and not dist.is_initialized():
         dist.init_process_group('nccl', device_id=torch.device(cfg.device))
-    edsr = isinstance(model, EDSR_1D)
-    tr = None if edsr else StofNetTrainer(model, lr=cfg.lr, weight_decay=cfg.weight_decay, lambda_value=cfg.lambda_value,
-                                          mask_amplitude=cfg.mask_amplitude, kernel_size=cfg.kernel_size, sigma=cfg.sigma,
-                                          precision=cfg.train_precision)
+    routed = isinstance(model, (EDSR_1D, ESPCN_1D))                     # the baselines with a `train_route` switch
+    tr = None if routed else StofNetTrainer(model, lr=cfg.lr, weight_decay=cfg.weight_decay, lambda_value=cfg.lambda_value,
+                                            mask_amplitude=cfg.mask_amplitude, kernel_size=cfg.kernel_size, sigma=cfg.sigma,
+                                            precision=cfg.train_precision)
     r, bs = int(cfg.upsample_factor), int(cfg.batch_size)
     n_val = max(bs, int(frames.shape[0] * 0.1) // bs * bs)              # held-out tail for early stopping
     tr_x, tr_gt = frames[:-n_val], gt[:-n_val]
@@ -236,14 +235,14 @@ def train(model, frames, gt, cfg, log=None):
         g = torch.where(g <= 0, torch.zeros_like(g), g)                  # main.py:217
         return torch.round(g.unsqueeze(1) * r).long()                    # main.py:218
 
-    autograd = edsr or str(getattr(cfg, 'trainer', 'fused')) == 'autograd'
+    autograd = routed or str(getattr(cfg, 'trainer', 'fused')) == 'autograd'
     if autograd:
         # the reference's own training lines (main.py:179-180,184-188,221-248,288) on the module's autograd boundary:
         # torch loss, torch.optim.AdamW, CosineAnnealingLR; `loss.backward()` runs the stof_train_* kernels
         import torch.nn.functional as F
         from stofnet_amd.mask2samples import coords2mask
         from stofnet_amd.training import allreduce_max_, allreduce_mean_, gaussian_kernel
-        if edsr:
+        if routed:
             route = str(getattr(cfg, 'train_route', 'kernels'))
             if route not in ('kernels', 'aten'):
                 raise ValueError(f"train_route must be 'kernels' or 'aten' (got {route!r})")

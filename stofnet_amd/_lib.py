@@ -206,6 +206,20 @@ _SIGNATURES = {
     'stof_train_edsr_out_wgrad_workspace_bytes': (_c.c_size_t, [_c.c_int32]),
     'stof_train_edsr_out_wgrad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_float,
                                              _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_train_espcn_repack_floats': (_c.c_size_t, []),
+    'stof_train_espcn_repack': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_train_espcn_in': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p]),
+    'stof_train_espcn_mid': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p]),
+    'stof_train_espcn_out': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_void_p]),
+    'stof_train_espcn_out_wgrad_workspace_bytes': (_c.c_size_t, [_c.c_int32]),
+    'stof_train_espcn_out_wgrad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32,
+                                              _c.c_float, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_train_espcn_out_dgrad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32,
+                                              _c.c_void_p]),
+    'stof_train_espcn_in_wgrad_workspace_bytes': (_c.c_size_t, []),
+    'stof_train_espcn_in_wgrad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_float,
+                                             _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_train_espcn_in_dgrad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_float, _c.c_void_p]),
     'stof_train_upsample_bwd_c': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_void_p]),
     'stof_train_sweep_blob_bytes': (_c.c_size_t, [_c.c_void_p]),
     'stof_train_sweep_pack': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),

@@ -21,7 +21,8 @@ EDSR_1D has a third route, opt-in with `train_route = 'kernels'`:
   forward_train_kernels(x)  the same network behind an autograd boundary (edsr_training.py): `loss.backward()` runs the
                             gfx950 training kernels in exact fp32, deterministic and free of MIOpen.
 
-With it `forward` takes the training kernels wherever it took `forward_aten` only because a graph is recorded."""
+With it `forward` takes the training kernels wherever it took `forward_aten` only because a graph is recorded.  ESPCN_1D
+has the same opt-in route (espcn_training.py: one kernel per stage, activations saved in device memory)."""
 import ctypes
 
 import torch
@@ -31,6 +32,7 @@ import torch.nn.functional as F
 from . import _lib
 from ._kernel_route import _KernelRoute, _pack
 from .edsr_training import EdsrFunction, EdsrTrainEngine
+from .espcn_training import EspcnFunction, EspcnTrainEngine
 from .sample_shuffle import SampleShuffle1D
 
 
@@ -153,6 +155,7 @@ class EDSR_1D(_KernelRoute, nn.Module):
 class ESPCN_1D(_KernelRoute, nn.Module):
     """models/espcn_1d.py:8-36: conv5 - tanh - conv3 - tanh - conv3 - SampleShuffle1D - sigmoid, with the reference's
     normal initialisation (std 0.001 for the layer fed by 32 channels, He-style otherwise, zero biases)."""
+    train_route = 'aten'            # 'aten' | 'kernels': which route `forward` takes when an autograd graph is recorded
     _KERNEL_CONFIG = 'an upscale_factor of at most 64'
 
     def __init__(self, upscale_factor):
@@ -196,6 +199,26 @@ class ESPCN_1D(_KernelRoute, nn.Module):
             _lib.check(_lib.lib().stof_espcn_forward(ctypes.byref(desc), _lib.ptr(x), N, L, _lib.ptr(packed), _lib.ptr(y),
                                                      _lib.ptr(logits), _lib.stream_ptr(x.device)), 'stof_espcn_forward')
         return y, logits
+
+    def forward_train_kernels(self, x):
+        """y [N, 1, L r] float32 on the gfx950 training kernels, with an autograd graph: its backward fills the gradient of
+        every parameter (and of x, if it asks for one) in exact fp32; raises where the kernels do not apply."""
+        self._check_kernels(x)
+        engines = self.__dict__.setdefault('_train_engines', {})
+        key = (str(x.device), int(self.sample_shuffle.upsample_factor))
+        engine = engines.get(key)
+        if engine is None:
+            engine = engines[key] = EspcnTrainEngine(x.device, key[1])
+        names, params = zip(*self.named_parameters())
+        return EspcnFunction.apply(x, engine, names, *params)
+
+    def forward(self, x):
+        if self.train_route not in ('aten', 'kernels'):
+            raise ValueError(f"ESPCN_1D.train_route must be 'aten' or 'kernels' (got {self.train_route!r})")
+        if (self.train_route == 'kernels' and self.kernels_supported(x) and torch.is_grad_enabled()
+                and (x.requires_grad or any(p.requires_grad for p in self._kernel_params()))):
+            return self.forward_train_kernels(x)
+        return super().forward(x)
 
     def forward_aten(self, x):
         x = torch.tanh(self.conv1(x))

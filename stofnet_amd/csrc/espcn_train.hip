@@ -1,0 +1,594 @@
+// Training ESPCN_1D(r) (models/espcn_1d.py:31-36), r = 1..64, in exact fp32, one kernel per stage with the activations saved in
+// HBM.  Activations are channel-last and un-gapped: h1 [N][L][64], h2 [N][L][32], x / dx [N][L], y / dy [N][L r]; every row
+// end is a predicate, so the zero padding of conv2 and conv3 is zeros of h1 and h2 (not tanh(bias)).
+//
+//   ep_in_kernel          h1 = tanh(conv1(x)), 1 -> 64, k 5                          (vector pipe)
+//   ep_repack_kernel      conv2.weight (32,64,3) -> the B-operand fragment image of ep_mid_kernel
+//   ep_mid_kernel         h2 = tanh(conv2(h1) + b2), 64 -> 32, k 3                   (v_mfma_f32_32x32x2_f32)
+//   ep_out_kernel         y = sigmoid(conv3(h2) + b3), 32 -> r, k 3                  (vector pipe)
+//   ep_out_wgrad_kernel   dW3 (r,32,3), db3 (r) from dz = dy y (1 - y) and h2
+//   ep_out_dgrad_kernel   g2 [N][L][32] = conv3^T(dz) (1 - h2^2)
+//   ep_in_wgrad_kernel    dW1 (64,1,5), db1 (64) from g' = g1 (1 - h1^2) and x
+//   ep_in_dgrad_kernel    dx [N][L] = conv1^T(g')
+//   ep_wgrad_reduce_kernel  the fixed-order sum over the partials of either weight gradient
+//
+// conv2's two gradient GEMMs are stof_train_wgrad(h1, g2) and stof_train_conv(g2, flipped W2) of train.hip: tanh' of conv2's
+// output is already in g2.
+//
+// The shuffle is free: in channel-last order z [N][L][r] IS the shuffled row [N][L r], one channel survives, so
+// y[n][l r + j] = sigmoid(z[n][l][j]).
+//
+// The rows of all waveforms are one flat sequence of N L rows; a tile of rows may span waveforms, the taps that would cross
+// a row end are skipped by t = row % L.  No float atomics: a weight-gradient work-group walks its 256-row chunks in a fixed
+// assignment (chunk k -> work-group k mod grid), keeps its sums in registers, folds them through LDS in a fixed order and
+// writes ONE partial; the reduce kernel adds the partials in a fixed order.  The order depends on the shape alone, so two
+// runs are bitwise equal.  h1, h2, g1, g2 and the fragment image must be 16-byte aligned.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "stof_common.h"
+#include "mfma32_frag.h"
+
+namespace {
+
+using stof_frag::f32x16;
+
+constexpr int C1 = 64, C2 = 32;             // channels of h1, h2
+constexpr int PT_ROWS = 64;                 // rows per work-group of ep_in_kernel and ep_out_dgrad_kernel
+constexpr int PM_TILE = 128;                // rows per work-group of ep_mid_kernel (4 waves x 32 rows)
+constexpr int PM_STRIDE = 68;               // LDS row stride of its h1 tile (floats): 16 lanes of a ds_read_b128 on 16 slots
+constexpr int PM_GROUPS = 3 * C1 / 8;       // K groups of conv2: k = tap * 64 + ci, 8 per group
+constexpr int PO_OUTS = 2048;               // outputs per work-group of ep_out_kernel (8 passes of 256)
+constexpr int PO_WS = 100;                  // LDS stride of one output channel's 96 conv3 weights
+constexpr int PW_CHUNK = 256;               // rows per chunk of the weight-gradient kernels
+constexpr int PW_SUB = 64;                  // rows per LDS stage of ep_out_wgrad_kernel
+constexpr int PW_MAX_COPIES = 512;          // partials (work-groups) of a weight-gradient launch
+constexpr int PW_IN_E = C1 * 5 + C1;        // floats of a conv1 partial: dw [f * 5 + d], then db [320 + f]
+constexpr int PD_TILE = 256;                // outputs per work-group of ep_in_dgrad_kernel
+constexpr int PD_ROWS = PD_TILE + 4 + 12;   // its tile with the 2-row halos, as 17 passes of 16 rows
+constexpr int64_t P_MAX_ROWS = (1ll << 25) - 1;      // N L 64 stays below 2^31
+
+inline bool r_ok(int32_t r) { return r >= 1 && r <= 64; }
+// N L within the range of the 32-bit indices (N, L >= 1)
+inline bool rows_ok(int64_t N, int64_t L) { return N <= P_MAX_ROWS / L; }
+__host__ __device__ inline int out_e(int r) { return r * (3 * C2 + 1); }                      // floats of a conv3 partial: dw, then db [r * 96 + j]
+
+__device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+// g (1 - s^2): the gradient through tanh, from the saved activation
+__device__ inline float4 tanh_bwd(float4 g, float4 s) {
+    return make_float4(g.x * fmaf(-s.x, s.x, 1.f), g.y * fmaf(-s.y, s.y, 1.f), g.z * fmaf(-s.z, s.z, 1.f), g.w * fmaf(-s.w, s.w, 1.f));
+}
+
+// ------------------------------------------------------------------------------------------------------------- conv1
+// Thread = (row slot tid >> 4, channels 4 q .. 4 q + 3): its twenty weights and four biases stay in registers for the four
+// rows it writes.  One output: bias, then taps 0..4 as one fmaf chain; a tap that leaves the waveform is skipped.
+__global__ __launch_bounds__(256) void ep_in_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                    float* __restrict__ h1, int total, int L) {
+    const int q = threadIdx.x & 15, slot = threadIdx.x >> 4;
+    float wr[4][5], br[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        br[i] = b[4 * q + i];
+#pragma unroll
+        for (int d = 0; d < 5; ++d) wr[i][d] = w[(4 * q + i) * 5 + d];
+    }
+    const int r0 = blockIdx.x * PT_ROWS + slot;
+    if (r0 >= total) return;
+    int t = r0 % L;
+#pragma unroll
+    for (int it = 0; it < PT_ROWS / 16; ++it) {
+        const int row = r0 + 16 * it;
+        if (row >= total) break;
+        float xv[5];
+        bool ok[5];
+#pragma unroll
+        for (int d = 0; d < 5; ++d) {
+            ok[d] = t + d - 2 >= 0 && t + d - 2 < L;
+            xv[d] = ok[d] ? x[row + d - 2] : 0.f;
+        }
+        float o[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float acc = br[i];
+#pragma unroll
+            for (int d = 0; d < 5; ++d) acc = ok[d] ? fmaf(wr[i][d], xv[d], acc) : acc;
+            o[i] = tanhf(acc);
+        }
+        *reinterpret_cast<float4*>(h1 + (size_t)row * C1 + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
+        t += 16;
+        if (t >= L) t %= L;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------- conv2
+// conv2.weight in torch layout (32,64,3) -> [24 K groups][64 lanes][4] in the fragment order of mfma32_frag.h with
+// k = tap * 64 + ci: lane (i = l & 31, h = l >> 5), element e of group q holds W[i][k = 8 q + 4 h + e].
+__global__ __launch_bounds__(256) void ep_repack_kernel(const float* __restrict__ w, float* __restrict__ out) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= PM_GROUPS * 256) return;
+    const int e = o & 3, lane = (o >> 2) & 63, q = o >> 8;
+    const int k = 8 * q + 4 * (lane >> 5) + e, tap = k / C1, ci = k % C1;
+    out[o] = w[((lane & 31) * C1 + ci) * 3 + tap];
+}
+
+// A work-group stages flat rows r0 - 1 .. r0 + PM_TILE of h1 in LDS (row j = flat row r0 - 1 + j, zero outside the buffer) and
+// wave w computes rows r0 + 32 w .. + 31: the A operand of lane (i, h) is the float4 at channel 8 (q & 7) + 4 h of row i + tap,
+// zeroed where that tap crosses the end of row i's waveform; the 32 output channels are the one N tile.  Eight accumulators,
+// K group q into accumulator q & 7 (one per 8-channel group, summed over the taps), added up in order at the end: as in
+// es_kernel of riders.hip, a single chain of 192 products loses about 3 bits more in the trained checkpoints.
+__global__ __launch_bounds__(256) void ep_mid_kernel(const float* __restrict__ h1, const float4* __restrict__ frag2,
+                                                     const float* __restrict__ b2, float* __restrict__ h2, int total, int L) {
+    __shared__ __attribute__((aligned(16))) float a1[(PM_TILE + 2) * PM_STRIDE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = lane & 31, h = lane >> 5;
+    const int r0 = blockIdx.x * PM_TILE;
+    for (int k = tid; k < (PM_TILE + 2) * 16; k += 256) {
+        const int j = k >> 4, c4 = k & 15;
+        const int row = r0 - 1 + j;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row >= 0 && row < total) v = ld4(h1 + (size_t)row * C1 + 4 * c4);
+        *reinterpret_cast<float4*>(a1 + j * PM_STRIDE + 4 * c4) = v;
+    }
+    __syncthreads();
+    if (r0 + 32 * wave >= total) return;
+    const int m = 32 * wave + i;
+    const int t = (r0 + m) % L;
+    const bool ok0 = t > 0, ok2 = t < L - 1;
+    const float* a = a1 + m * PM_STRIDE + 4 * h;
+    const float4* bq = frag2 + lane;
+    f32x16 acc8[8] = {};
+    float4 bv = bq[0];
+#pragma unroll
+    for (int q = 0; q < PM_GROUPS; ++q) {
+        const int tap = q >> 3;
+        float4 av = *reinterpret_cast<const float4*>(a + tap * PM_STRIDE + 8 * (q & 7));
+        if ((tap == 0 && !ok0) || (tap == 2 && !ok2)) av = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 cb = bv;
+        if (q + 1 < PM_GROUPS) bv = bq[(q + 1) * 64];
+        acc8[q & 7] = MFMA32(av.x, cb.x, acc8[q & 7]);
+        acc8[q & 7] = MFMA32(av.y, cb.y, acc8[q & 7]);
+        acc8[q & 7] = MFMA32(av.z, cb.z, acc8[q & 7]);
+        acc8[q & 7] = MFMA32(av.w, cb.w, acc8[q & 7]);
+    }
+    f32x16 acc = acc8[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) acc += acc8[j];
+    const float b = b2[i];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int row = r0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (row < total) h2[(size_t)row * C2 + i] = tanhf(acc[e] + b);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------- conv3
+// Thread: output o = row r + j.  The r x 96 weights go through LDS as [j][tap][c]; bias, then taps 0..2 over channels 0..31 as
+// one fmaf chain (a tap that leaves the waveform is skipped), then the sigmoid as es_kernel computes it.
+__global__ __launch_bounds__(256) void ep_out_kernel(const float* __restrict__ h2, const float* __restrict__ w, const float* __restrict__ b,
+                                                     float* __restrict__ y, int total_out, int L, int r) {
+    __shared__ __attribute__((aligned(16))) float ws[64 * PO_WS];
+    const int tid = threadIdx.x;
+    for (int k = tid; k < r * 3 * C2; k += 256) {
+        const int j = k / (3 * C2), rem = k - j * (3 * C2), c = rem / 3, tap = rem - 3 * c;
+        ws[j * PO_WS + tap * C2 + c] = w[k];
+    }
+    __syncthreads();
+    const long long o0 = (long long)blockIdx.x * PO_OUTS + tid;
+    for (int it = 0; it < PO_OUTS / 256; ++it) {
+        const long long o = o0 + 256 * it;
+        if (o >= total_out) break;
+        const int row = (int)(o / r), j = (int)(o - (long long)row * r), t = row % L;
+        const float* wj = ws + j * PO_WS;
+        float acc = b[j];
+#pragma unroll
+        for (int tap = 0; tap < 3; ++tap) {
+            if ((tap == 0 && t == 0) || (tap == 2 && t == L - 1)) continue;
+            const float* p = h2 + ((long long)row + tap - 1) * C2;
+#pragma unroll
+            for (int c = 0; c < C2; c += 4) {
+                const float4 v = ld4(p + c), u = *reinterpret_cast<const float4*>(wj + tap * C2 + c);
+                acc = fmaf(u.x, v.x, acc);
+                acc = fmaf(u.y, v.y, acc);
+                acc = fmaf(u.z, v.z, acc);
+                acc = fmaf(u.w, v.w, acc);
+            }
+        }
+        y[o] = 1.f / (1.f + expf(-acc));
+    }
+}
+
+// g2[row][c] = (1 - h2[row][c]^2) sum_tap sum_j w[j][c][tap] dz[row - tap + 1][j], dz = dy y (1 - y), the terms outside the
+// waveform dropped.  A work-group takes PT_ROWS rows: the weights go through LDS as [tap][j][c], the dz tile with its one-row
+// halos as [row][r | 1]; thread = (row slot tid >> 3, channels 4 c4 .. + 3), two rows per thread.  Per tap one fmaf chain over
+// j = 0 .. r - 1, the three taps' sums added in the order 1, 0, 2.
+__global__ __launch_bounds__(256) void ep_out_dgrad_kernel(const float* __restrict__ y, const float* __restrict__ dy,
+                                                           const float* __restrict__ h2, const float* __restrict__ w,
+                                                           float* __restrict__ g2, int total, int L, int r) {
+    __shared__ __attribute__((aligned(16))) float wt[3 * 64 * C2];
+    __shared__ float dzs[(PT_ROWS + 2) * 65];
+    const int tid = threadIdx.x, c4 = tid & 7, slot = tid >> 3;
+    const int r0 = blockIdx.x * PT_ROWS, rs = r | 1;
+    for (int k = tid; k < r * 3 * C2; k += 256) {
+        const int j = k / (3 * C2), rem = k - j * (3 * C2), c = rem / 3, tap = rem - 3 * c;
+        wt[(tap * 64 + j) * C2 + c] = w[k];
+    }
+    for (int k = tid; k < (PT_ROWS + 2) * r; k += 256) {
+        const int lr = k / r, j = k - lr * r;
+        const long long row = (long long)r0 - 1 + lr;
+        float v = 0.f;
+        if (row >= 0 && row < total) {
+            const float yv = y[row * r + j];
+            v = dy[row * r + j] * yv * (1.f - yv);
+        }
+        dzs[lr * rs + j] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < PT_ROWS / 32; ++it) {
+        const int lr = slot + 32 * it, row = r0 + lr;
+        if (row >= total) break;
+        const int t = row % L;
+        float s[3][4];
+#pragma unroll
+        for (int tap = 0; tap < 3; ++tap) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s[tap][i] = 0.f;
+            if ((tap == 0 && t == L - 1) || (tap == 2 && t == 0)) continue;       // tap 0 meets row + 1, tap 2 row - 1
+            const float* dz = dzs + (lr + 2 - tap) * rs;                          // LDS row of flat row `row - tap + 1`
+            const float* wp = wt + tap * 64 * C2 + 4 * c4;
+            for (int j = 0; j < r; ++j) {
+                const float4 u = *reinterpret_cast<const float4*>(wp + j * C2);
+                const float d = dz[j];
+                s[tap][0] = fmaf(u.x, d, s[tap][0]);
+                s[tap][1] = fmaf(u.y, d, s[tap][1]);
+                s[tap][2] = fmaf(u.z, d, s[tap][2]);
+                s[tap][3] = fmaf(u.w, d, s[tap][3]);
+            }
+        }
+        const size_t at = (size_t)row * C2 + 4 * c4;
+        const float4 g = make_float4((s[1][0] + s[0][0]) + s[2][0], (s[1][1] + s[0][1]) + s[2][1], (s[1][2] + s[0][2]) + s[2][2],
+                                     (s[1][3] + s[0][3]) + s[2][3]);
+        *reinterpret_cast<float4*>(g2 + at) = tanh_bwd(g, ld4(h2 + at));
+    }
+}
+
+// dw[j][c][tap] = sum_rows dz[row][j] h2[row + tap - 1][c], db[j] = sum_rows dz[row][j].  A chunk goes through LDS in four
+// stages of PW_SUB rows (h2 with one-row halos, dz as [row][r | 1]).  Thread = (channels 4 c4 .. + 3, j slot, row part):
+// with JS = min(32, r rounded up to a power of two) j slots the 32 thread groups split into P = 32 / JS row parts, part p
+// taking rows p, p + P, ... of a stage; a thread serves j = slot and slot + 32.  The P parts are added in order through LDS.
+__global__ __launch_bounds__(256) void ep_out_wgrad_kernel(const float* __restrict__ h2, const float* __restrict__ y,
+                                                           const float* __restrict__ dy, float* __restrict__ copies, int total, int L,
+                                                           int r, int js_log2) {
+    __shared__ __attribute__((aligned(16))) float hs[(PW_SUB + 2) * C2];
+    __shared__ float dzs[PW_SUB * 65];
+    __shared__ float red[256 * 27];
+    const int tid = threadIdx.x, c4 = tid & 7, grp = tid >> 3;
+    const int JS = 1 << js_log2, P = 32 >> js_log2, jslot = grp & (JS - 1), part = grp >> js_log2;
+    const int j0 = jslot, j1 = jslot + 32, rs = r | 1;
+    const bool act0 = j0 < r, act1 = j1 < r;
+    float acc[2][4][3], sb[2] = {0.f, 0.f};
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) acc[a][i][d] = 0.f;
+    for (long long c0 = (long long)blockIdx.x * PW_CHUNK; c0 < total; c0 += (long long)gridDim.x * PW_CHUNK) {
+        for (int sub = 0; sub < PW_CHUNK / PW_SUB; ++sub) {
+            const int s0 = (int)c0 + PW_SUB * sub;
+            if (s0 >= total) break;
+            __syncthreads();
+            for (int k = tid; k < (PW_SUB + 2) * 8; k += 256) {
+                const int row = s0 - 1 + (k >> 3);
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (row >= 0 && row < total) v = ld4(h2 + (size_t)row * C2 + 4 * (k & 7));
+                *reinterpret_cast<float4*>(hs + 4 * k) = v;
+            }
+            for (int k = tid; k < PW_SUB * r; k += 256) {
+                const int lr = k / r, j = k - lr * r;
+                float v = 0.f;
+                if (s0 + lr < total) {
+                    const long long at = (long long)s0 * r + k;
+                    const float yv = y[at];
+                    v = dy[at] * yv * (1.f - yv);
+                }
+                dzs[lr * rs + j] = v;
+            }
+            __syncthreads();
+            int t = (s0 + part) % L;
+            for (int lr = part; lr < PW_SUB; lr += P) {
+                if (s0 + lr >= total) break;
+                const float d[2] = {act0 ? dzs[lr * rs + j0] : 0.f, act1 ? dzs[lr * rs + j1] : 0.f};
+                const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 hm = t > 0 ? *reinterpret_cast<const float4*>(hs + lr * C2 + 4 * c4) : z4;
+                const float4 hc = *reinterpret_cast<const float4*>(hs + (lr + 1) * C2 + 4 * c4);
+                const float4 hp = t < L - 1 ? *reinterpret_cast<const float4*>(hs + (lr + 2) * C2 + 4 * c4) : z4;
+                const float hv[3][4] = {{hm.x, hm.y, hm.z, hm.w}, {hc.x, hc.y, hc.z, hc.w}, {hp.x, hp.y, hp.z, hp.w}};
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) acc[a][i][k] = fmaf(d[a], hv[k][i], acc[a][i][k]);
+                    sb[a] += d[a];
+                }
+                t += P;
+                if (t >= L) t %= L;
+            }
+        }
+    }
+    __syncthreads();
+    float* mine = red + tid * 27;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) mine[a * 13 + i * 3 + k] = acc[a][i][k];
+        mine[a * 13 + 12] = sb[a];
+    }
+    __syncthreads();
+    if (part != 0) return;
+    float* copy = copies + (size_t)blockIdx.x * out_e(r);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const int j = a ? j1 : j0;
+        if (j >= r) continue;
+        for (int e = 0; e < 13; ++e) {
+            float s = mine[a * 13 + e];
+            for (int p = 1; p < P; ++p) s += red[(tid + p * JS * 8) * 27 + a * 13 + e];
+            if (e < 12) copy[(j * C2 + 4 * c4 + e / 3) * 3 + e % 3] = s;
+            else if (c4 == 0) copy[r * 3 * C2 + j] = s;
+        }
+    }
+}
+
+// out[e] = out_scale * sum over the `ncopies` partials of E floats, element e < ndw -> dw[e], else db[e - ndw]: 64 elements x
+// 16 interleaved slices of the copies per work-group, four chains per slice, combined through LDS in a fixed order (the
+// scheme of ed_wgrad_reduce_kernel of edsr_train.hip).
+__global__ __launch_bounds__(1024) void ep_wgrad_reduce_kernel(const float* __restrict__ copies, int ncopies, int stride, int E, int ndw,
+                                                               float* __restrict__ dw, float* __restrict__ db, float out_scale) {
+    __shared__ float red[16][64];
+    const int e = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int i = blockIdx.x * 64 + e;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    if (i < E) {
+        int k = sl;
+        for (; k + 48 < ncopies; k += 64) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] += copies[(size_t)(k + 16 * j) * stride + i];
+        }
+        for (; k < ncopies; k += 16) a[0] += copies[(size_t)k * stride + i];
+    }
+    red[sl][e] = (a[0] + a[1]) + (a[2] + a[3]);
+    __syncthreads();
+    if (sl != 0 || i >= E) return;
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; k += 4) s += (red[k][e] + red[k + 1][e]) + (red[k + 2][e] + red[k + 3][e]);
+    if (i < ndw) dw[i] = s * out_scale; else db[i - ndw] = s * out_scale;
+}
+
+// ------------------------------------------------------------------------------------------------- conv1, backward
+// dw[f][d] = sum_rows g'[row][f] x[t + d - 2], db[f] = sum_rows g'[row][f].  Thread = (row slot tid >> 4, channels 4 q .. + 3)
+// with 24 sums [channel i][tap 0..4 | plain sum]; the 16 row slots are added pairwise in a fixed order through LDS.
+__global__ __launch_bounds__(256) void ep_in_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ h1,
+                                                          float* __restrict__ copies, int total, int L) {
+    __shared__ float red[16 * PW_IN_E];
+    const int tid = threadIdx.x, q = tid & 15, slot = tid >> 4;
+    float acc[4][6];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc[i][k] = 0.f;
+    for (long long c0 = (long long)blockIdx.x * PW_CHUNK; c0 < total; c0 += (long long)gridDim.x * PW_CHUNK) {
+        const int r0 = (int)c0 + slot;
+        int t = r0 % L;
+#pragma unroll 4
+        for (int it = 0; it < PW_CHUNK / 16; ++it) {
+            const int row = r0 + 16 * it;
+            if (row >= total) break;
+            const size_t at = (size_t)row * C1 + 4 * q;
+            const float4 v = tanh_bwd(ld4(g + at), ld4(h1 + at));
+            const float gv[4] = {v.x, v.y, v.z, v.w};
+            float xv[5];
+#pragma unroll
+            for (int d = 0; d < 5; ++d) xv[d] = (t + d - 2 >= 0 && t + d - 2 < L) ? x[row + d - 2] : 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                for (int d = 0; d < 5; ++d) acc[i][d] = fmaf(gv[i], xv[d], acc[i][d]);
+                acc[i][5] += gv[i];
+            }
+            t += 16;
+            if (t >= L) t %= L;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) red[slot * PW_IN_E + q * 24 + i * 6 + k] = acc[i][k];
+    __syncthreads();
+    for (int el = tid; el < PW_IN_E; el += 256) {
+        float s[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            s[k] = (red[(4 * k) * PW_IN_E + el] + red[(4 * k + 1) * PW_IN_E + el]) +
+                   (red[(4 * k + 2) * PW_IN_E + el] + red[(4 * k + 3) * PW_IN_E + el]);
+        const int f = 4 * (el / 24) + (el % 24) / 6, k = el % 6;
+        copies[(size_t)blockIdx.x * PW_IN_E + (k < 5 ? f * 5 + k : C1 * 5 + f)] = (s[0] + s[1]) + (s[2] + s[3]);
+    }
+}
+
+// dx[row] = out_scale * sum_d p_d[row - d + 2] with p_d[row] = sum_f w[f][d] g'[row][f], a term dropped where row - d + 2 leaves
+// the waveform; the terms are added in the order d = 2, 1, 3, 0, 4.  A work-group takes PD_TILE outputs: the 16 lanes of a
+// row each form their four channels' share of the five dot products, a fixed xor butterfly over the 16 lanes adds them, the
+// 260 x 5 sums go through LDS.
+__global__ __launch_bounds__(256) void ep_in_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ h1, const float* __restrict__ w,
+                                                          float* __restrict__ dx, int total, int L, float out_scale) {
+    __shared__ float ps[5][PD_ROWS];                         // [tap][row r0 - 2 + j], j < 260
+    const int tid = threadIdx.x, q = tid & 15, slot = tid >> 4;
+    float wr[4][5];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int d = 0; d < 5; ++d) wr[i][d] = w[(4 * q + i) * 5 + d];
+    const long long r0 = (long long)blockIdx.x * PD_TILE;
+    for (int j = slot; j < PD_ROWS; j += 16) {               // (every lane of a wave stays in the loop: the butterfly needs all 16)
+        const long long row = r0 - 2 + j;
+        float p[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        if (j < PD_TILE + 4 && row >= 0 && row < total) {
+            const size_t at = (size_t)row * C1 + 4 * q;
+            const float4 v = tanh_bwd(ld4(g + at), ld4(h1 + at));
+            const float gv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int d = 0; d < 5; ++d)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) p[d] = fmaf(wr[i][d], gv[i], p[d]);
+        }
+#pragma unroll
+        for (int d = 0; d < 5; ++d) {
+#pragma unroll
+            for (int m = 8; m >= 1; m >>= 1) p[d] += __shfl_xor(p[d], m, 16);
+        }
+        if (q == 0) {
+#pragma unroll
+            for (int d = 0; d < 5; ++d) ps[d][j] = p[d];
+        }
+    }
+    __syncthreads();
+    const long long row = r0 + tid;
+    if (row >= total) return;
+    const int t = (int)(row % L), j = tid + 2;
+    float s = ps[2][j];
+    if (t + 1 < L) s += ps[1][j + 1];
+    if (t >= 1) s += ps[3][j - 1];
+    if (t + 2 < L) s += ps[0][j + 2];
+    if (t >= 2) s += ps[4][j - 2];
+    dx[row] = s * out_scale;
+}
+
+inline int wgrad_copies(int64_t rows) {
+    const int64_t chunks = (rows + PW_CHUNK - 1) / PW_CHUNK;
+    return (int)(chunks < PW_MAX_COPIES ? chunks : PW_MAX_COPIES);
+}
+constexpr size_t PW_IN_WORKSPACE = (size_t)PW_MAX_COPIES * PW_IN_E * sizeof(float);
+inline size_t out_workspace(int r) { return (size_t)PW_MAX_COPIES * out_e(r) * sizeof(float); }
+
+inline int launched() { return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP; }
+
+}  // namespace
+
+extern "C" size_t stof_train_espcn_repack_floats(void) { return (size_t)PM_GROUPS * 256; }
+
+extern "C" int stof_train_espcn_repack(const float* w2, float* out, void* stream) {
+    if (!w2 || !out) return STOF_ERR_BAD_ARG;
+    hipLaunchKernelGGL(ep_repack_kernel, dim3(PM_GROUPS), dim3(256), 0, static_cast<hipStream_t>(stream), w2, out);
+    return launched();
+}
+
+extern "C" int stof_train_espcn_in(const float* x, const float* w, const float* b, float* h1, int64_t N, int64_t L, void* stream) {
+    if (N < 0 || L < 0) return STOF_ERR_BAD_ARG;
+    if (N == 0 || L == 0) return STOF_OK;
+    if (!x || !w || !b || !h1) return STOF_ERR_BAD_ARG;
+    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int total = (int)(N * L);
+    hipLaunchKernelGGL(ep_in_kernel, dim3((unsigned)((total + PT_ROWS - 1) / PT_ROWS)), dim3(256), 0, static_cast<hipStream_t>(stream), x, w,
+                       b, h1, total, (int)L);
+    return launched();
+}
+
+extern "C" int stof_train_espcn_mid(const float* h1, const float* frag2, const float* b2, float* h2, int64_t N, int64_t L, void* stream) {
+    if (N < 0 || L < 0) return STOF_ERR_BAD_ARG;
+    if (N == 0 || L == 0) return STOF_OK;
+    if (!h1 || !frag2 || !b2 || !h2) return STOF_ERR_BAD_ARG;
+    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int total = (int)(N * L);
+    hipLaunchKernelGGL(ep_mid_kernel, dim3((unsigned)((total + PM_TILE - 1) / PM_TILE)), dim3(256), 0, static_cast<hipStream_t>(stream), h1,
+                       reinterpret_cast<const float4*>(frag2), b2, h2, total, (int)L);
+    return launched();
+}
+
+extern "C" int stof_train_espcn_out(const float* h2, const float* w, const float* b, float* y, int64_t N, int64_t L, int32_t r,
+                                    void* stream) {
+    if (N < 0 || L < 0 || !r_ok(r)) return STOF_ERR_BAD_ARG;
+    if (N == 0 || L == 0) return STOF_OK;
+    if (!h2 || !w || !b || !y) return STOF_ERR_BAD_ARG;
+    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const long long total = N * L * r;
+    hipLaunchKernelGGL(ep_out_kernel, dim3((unsigned)((total + PO_OUTS - 1) / PO_OUTS)), dim3(256), 0, static_cast<hipStream_t>(stream), h2, w,
+                       b, y, (int)total, (int)L, (int)r);
+    return launched();
+}
+
+extern "C" size_t stof_train_espcn_out_wgrad_workspace_bytes(int32_t r) { return r_ok(r) ? out_workspace(r) : 0; }
+
+extern "C" int stof_train_espcn_out_wgrad(const float* h2, const float* y, const float* dy, float* dw, float* db, int64_t N, int64_t L,
+                                          int32_t r, float out_scale, void* workspace, size_t workspace_bytes, void* stream) {
+    if (N < 0 || L < 0 || !r_ok(r) || !dw || !db) return STOF_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (N == 0 || L == 0) {
+        if (hipMemsetAsync(dw, 0, (size_t)r * C2 * 3 * sizeof(float), s) != hipSuccess ||
+            hipMemsetAsync(db, 0, (size_t)r * sizeof(float), s) != hipSuccess)
+            return STOF_ERR_HIP;
+        return STOF_OK;
+    }
+    if (!h2 || !y || !dy || !workspace) return STOF_ERR_BAD_ARG;
+    if (workspace_bytes < out_workspace(r)) return STOF_ERR_WORKSPACE;
+    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    float* copies = static_cast<float*>(workspace);
+    const int gx = wgrad_copies(N * L);
+    int js_log2 = 0;
+    while ((1 << js_log2) < r && js_log2 < 5) ++js_log2;
+    hipLaunchKernelGGL(ep_out_wgrad_kernel, dim3((unsigned)gx), dim3(256), 0, s, h2, y, dy, copies, (int)(N * L), (int)L, (int)r, js_log2);
+    if (launched() != STOF_OK) return STOF_ERR_HIP;
+    const int E = out_e(r);
+    hipLaunchKernelGGL(ep_wgrad_reduce_kernel, dim3((unsigned)((E + 63) / 64)), dim3(1024), 0, s, copies, gx, E, E, r * 3 * C2, dw, db,
+                       out_scale);
+    return launched();
+}
+
+extern "C" int stof_train_espcn_out_dgrad(const float* y, const float* dy, const float* h2, const float* w, float* g2, int64_t N, int64_t L,
+                                          int32_t r, void* stream) {
+    if (N < 0 || L < 0 || !r_ok(r)) return STOF_ERR_BAD_ARG;
+    if (N == 0 || L == 0) return STOF_OK;
+    if (!y || !dy || !h2 || !w || !g2) return STOF_ERR_BAD_ARG;
+    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int total = (int)(N * L);
+    hipLaunchKernelGGL(ep_out_dgrad_kernel, dim3((unsigned)((total + PT_ROWS - 1) / PT_ROWS)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       y, dy, h2, w, g2, total, (int)L, (int)r);
+    return launched();
+}
+
+extern "C" size_t stof_train_espcn_in_wgrad_workspace_bytes(void) { return PW_IN_WORKSPACE; }
+
+extern "C" int stof_train_espcn_in_wgrad(const float* x, const float* g1, const float* h1, float* dw, float* db, int64_t N, int64_t L,
+                                         float out_scale, void* workspace, size_t workspace_bytes, void* stream) {
+    if (N < 0 || L < 0 || !dw || !db) return STOF_ERR_BAD_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (N == 0 || L == 0) {
+        if (hipMemsetAsync(dw, 0, C1 * 5 * sizeof(float), s) != hipSuccess || hipMemsetAsync(db, 0, C1 * sizeof(float), s) != hipSuccess)
+            return STOF_ERR_HIP;
+        return STOF_OK;
+    }
+    if (!x || !g1 || !h1 || !workspace) return STOF_ERR_BAD_ARG;
+    if (workspace_bytes < PW_IN_WORKSPACE) return STOF_ERR_WORKSPACE;
+    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    float* copies = static_cast<float*>(workspace);
+    const int gx = wgrad_copies(N * L);
+    hipLaunchKernelGGL(ep_in_wgrad_kernel, dim3((unsigned)gx), dim3(256), 0, s, x, g1, h1, copies, (int)(N * L), (int)L);
+    if (launched() != STOF_OK) return STOF_ERR_HIP;
+    hipLaunchKernelGGL(ep_wgrad_reduce_kernel, dim3(PW_IN_E / 64), dim3(1024), 0, s, copies, gx, PW_IN_E, PW_IN_E, C1 * 5, dw, db, out_scale);
+    return launched();
+}
+
+extern "C" int stof_train_espcn_in_dgrad(const float* g1, const float* h1, const float* w, float* dx, int64_t N, int64_t L, float out_scale,
+                                         void* stream) {
+    if (N < 0 || L < 0) return STOF_ERR_BAD_ARG;
+    if (N == 0 || L == 0) return STOF_OK;
+    if (!g1 || !h1 || !w || !dx) return STOF_ERR_BAD_ARG;
+    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int total = (int)(N * L);
+    hipLaunchKernelGGL(ep_in_dgrad_kernel, dim3((unsigned)((total + PD_TILE - 1) / PD_TILE)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       g1, h1, w, dx, total, (int)L, out_scale);
+    return launched();
+}
