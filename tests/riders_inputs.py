@@ -5,6 +5,8 @@ The whole batch of a case runs; the fixture keeps `kept_rows` of its outputs (ro
 intermediate (the input of `upscale`, [N, 64, L]) it keeps, for the last kept row, the first and last TRUNK_EDGE samples
 of every channel (`trunk_edges`)."""
 import numpy as np
+import torch
+import torch.nn.functional as F
 
 from stofnet_amd import synth
 
@@ -86,3 +88,31 @@ def weights(wkey, load, *shape):
     if isinstance(wkey, str):
         return load(wkey)
     return seeded_edsr(*shape, wkey) if len(shape) == 2 else seeded_espcn(*shape, wkey)
+
+
+# float64 torch-CPU restatements of the two networks (tests/test_riders_cpu.py pins them against the fixture)
+def shuffle64(x, r):
+    """SampleShuffle1D (utils/sample_shuffle.py:24-27): out[n, c, w r + k] = in[n, k C + c, w]"""
+    n, cin, w = x.shape
+    return x.view(n, r, cin // r, w).permute(0, 2, 3, 1).contiguous().view(n, cin // r, w * r)
+
+
+def edsr64(sd, num_blocks, r, x):
+    """EDSR_1D.forward in float64 on torch CPU -> (y [N, 1, L r], the input of upscale [N, 64, L])"""
+    d = lambda k: torch.from_numpy(np.asarray(sd[k], np.float64))     # noqa: E731
+    conv = lambda a, k: F.conv1d(a, d(k + '.weight'), d(k + '.bias'), padding=1)     # noqa: E731
+    first = F.relu(conv(torch.from_numpy(np.asarray(x, np.float64)), 'conv_input'))
+    out = first
+    for b in range(num_blocks):
+        out = conv(F.relu(conv(out, f'residual_blocks.{b}.conv1')), f'residual_blocks.{b}.conv2') + out
+    trunk = conv(out, 'conv_mid') + first
+    return conv(shuffle64(trunk, r), 'conv_output').numpy(), trunk.numpy()
+
+
+def espcn64(sd, r, x):
+    """ESPCN_1D.forward in float64 on torch CPU -> (y [N, 1, L r], the logits [N, 1, L r])"""
+    d = lambda k: torch.from_numpy(np.asarray(sd[k], np.float64))     # noqa: E731
+    a = torch.tanh(F.conv1d(torch.from_numpy(np.asarray(x, np.float64)), d('conv1.weight'), d('conv1.bias'), padding=2))
+    a = torch.tanh(F.conv1d(a, d('conv2.weight'), d('conv2.bias'), padding=1))
+    logits = shuffle64(F.conv1d(a, d('conv3.weight'), d('conv3.bias'), padding=1), r)
+    return torch.sigmoid(logits).numpy(), logits.numpy()
