@@ -56,6 +56,33 @@ def pack_espcn_weights(upscale_factor, params):
                  'stof_espcn_pack_weights')
 
 
+class _TrainRoute(_KernelRoute):
+    """`_KernelRoute` of a model that can also train on the gfx950 kernels: `train_route = 'kernels'` makes `forward` take
+    `forward_train_kernels` wherever it took `forward_aten` only because an autograd graph is recorded.  A model supplies
+    `_train_engine_key()` (what its engine depends on besides the device), `_make_train_engine(dev, key)` and
+    `_train_function`, the engine's autograd boundary."""
+    train_route = 'aten'            # 'aten' | 'kernels': which route `forward` takes when an autograd graph is recorded
+
+    def forward_train_kernels(self, x):
+        """y [N, 1, L r] float32 on the gfx950 training kernels, with an autograd graph: its backward fills the gradient of
+        every parameter (and of x, if it asks for one) in exact fp32; raises where the kernels do not apply."""
+        self._check_kernels(x)
+        engines = self.__dict__.setdefault('_train_engines', {})
+        key = (str(x.device), *self._train_engine_key())
+        if key not in engines:
+            engines[key] = self._make_train_engine(x.device, key[1:])
+        names, params = zip(*self.named_parameters())
+        return self._train_function.apply(x, engines[key], names, *params)
+
+    def forward(self, x):
+        if self.train_route not in ('aten', 'kernels'):
+            raise ValueError(f"{type(self).__name__}.train_route must be 'aten' or 'kernels' (got {self.train_route!r})")
+        if (self.train_route == 'kernels' and self.kernels_supported(x) and torch.is_grad_enabled()
+                and (x.requires_grad or any(p.requires_grad for p in self._kernel_params()))):
+            return self.forward_train_kernels(x)
+        return super().forward(x)
+
+
 class ResidualBlock(nn.Module):
     """conv3 - ReLU - conv3 plus identity (models/edsr_1d.py:8-19)."""
 
@@ -69,12 +96,12 @@ class ResidualBlock(nn.Module):
         return self.conv2(self.relu(self.conv1(x))) + x
 
 
-class EDSR_1D(_KernelRoute, nn.Module):
+class EDSR_1D(_TrainRoute, nn.Module):
     """models/edsr_1d.py:22-45: input conv + ReLU, `num_blocks` residual blocks, mid conv with the long skip,
     SampleShuffle1D (C = num_features / upscale_factor channels survive), output conv."""
     max_workspace_bytes = 512 << 20
-    train_route = 'aten'            # 'aten' | 'kernels': which route `forward` takes when an autograd graph is recorded
     _KERNEL_CONFIG = 'num_channels = 1, num_features = 64 and an upscale_factor that divides 64'
+    _train_function = EdsrFunction
 
     def __init__(self, num_channels=1, num_features=64, num_blocks=8, upscale_factor=4):
         super().__init__()
@@ -123,25 +150,11 @@ class EDSR_1D(_KernelRoute, nn.Module):
         self._chunked(x.device, N, lambda n: int(lib.stof_edsr_workspace_bytes(ctypes.byref(desc), n, L)), launch)
         return y, trunk
 
-    def forward_train_kernels(self, x):
-        """y [N, 1, L r] float32 on the gfx950 training kernels, with an autograd graph: its backward fills the gradient of
-        every parameter (and of x, if it asks for one) in exact fp32; raises where the kernels do not apply."""
-        self._check_kernels(x)
-        engines = self.__dict__.setdefault('_train_engines', {})
-        key = (str(x.device), len(self.residual_blocks), int(self.upscale.upsample_factor))
-        engine = engines.get(key)
-        if engine is None:
-            engine = engines[key] = EdsrTrainEngine(x.device, key[1], key[2])
-        names, params = zip(*self.named_parameters())
-        return EdsrFunction.apply(x, engine, names, *params)
+    def _train_engine_key(self):
+        return len(self.residual_blocks), int(self.upscale.upsample_factor)
 
-    def forward(self, x):
-        if self.train_route not in ('aten', 'kernels'):
-            raise ValueError(f"EDSR_1D.train_route must be 'aten' or 'kernels' (got {self.train_route!r})")
-        if (self.train_route == 'kernels' and self.kernels_supported(x) and torch.is_grad_enabled()
-                and (x.requires_grad or any(p.requires_grad for p in self._kernel_params()))):
-            return self.forward_train_kernels(x)
-        return super().forward(x)
+    def _make_train_engine(self, dev, key):
+        return EdsrTrainEngine(dev, *key)
 
     def forward_aten(self, x):
         first = self.relu(self.conv_input(x))
@@ -152,11 +165,11 @@ class EDSR_1D(_KernelRoute, nn.Module):
         return self.conv_output(self.upscale(out))
 
 
-class ESPCN_1D(_KernelRoute, nn.Module):
+class ESPCN_1D(_TrainRoute, nn.Module):
     """models/espcn_1d.py:8-36: conv5 - tanh - conv3 - tanh - conv3 - SampleShuffle1D - sigmoid, with the reference's
     normal initialisation (std 0.001 for the layer fed by 32 channels, He-style otherwise, zero biases)."""
-    train_route = 'aten'            # 'aten' | 'kernels': which route `forward` takes when an autograd graph is recorded
     _KERNEL_CONFIG = 'an upscale_factor of at most 64'
+    _train_function = EspcnFunction
 
     def __init__(self, upscale_factor):
         super().__init__()
@@ -200,25 +213,11 @@ class ESPCN_1D(_KernelRoute, nn.Module):
                                                      _lib.ptr(logits), _lib.stream_ptr(x.device)), 'stof_espcn_forward')
         return y, logits
 
-    def forward_train_kernels(self, x):
-        """y [N, 1, L r] float32 on the gfx950 training kernels, with an autograd graph: its backward fills the gradient of
-        every parameter (and of x, if it asks for one) in exact fp32; raises where the kernels do not apply."""
-        self._check_kernels(x)
-        engines = self.__dict__.setdefault('_train_engines', {})
-        key = (str(x.device), int(self.sample_shuffle.upsample_factor))
-        engine = engines.get(key)
-        if engine is None:
-            engine = engines[key] = EspcnTrainEngine(x.device, key[1])
-        names, params = zip(*self.named_parameters())
-        return EspcnFunction.apply(x, engine, names, *params)
+    def _train_engine_key(self):
+        return (int(self.sample_shuffle.upsample_factor),)
 
-    def forward(self, x):
-        if self.train_route not in ('aten', 'kernels'):
-            raise ValueError(f"ESPCN_1D.train_route must be 'aten' or 'kernels' (got {self.train_route!r})")
-        if (self.train_route == 'kernels' and self.kernels_supported(x) and torch.is_grad_enabled()
-                and (x.requires_grad or any(p.requires_grad for p in self._kernel_params()))):
-            return self.forward_train_kernels(x)
-        return super().forward(x)
+    def _make_train_engine(self, dev, key):
+        return EspcnTrainEngine(dev, *key)
 
     def forward_aten(self, x):
         x = torch.tanh(self.conv1(x))

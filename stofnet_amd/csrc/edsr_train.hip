@@ -8,7 +8,8 @@
 //   ed_out_kernel         y [N][L r] = conv_output(SampleShuffle1D(r)(trunk))
 //   ed_out_dgrad_kernel   dtrunk [N][L][64] = shuffle^T(conv_output^T(dy))
 //   ed_out_wgrad_kernel   dw (1,64/r,3), db (1)
-//   ed_wgrad_reduce_kernel  the fixed-order sum over the partials of either weight gradient
+// conv_input's three kernels are the shared input end of train_ends.h (K = 3, ReLU); the partials of either weight gradient are
+// added by partial_reduce_kernel of wgrad_reduce.h.
 //
 // The shuffle is free in this layout: with C = 64 / r, the C channels of shuffled sample m of waveform n are the floats
 // (n L r + m) C .. + C - 1 of the trunk buffer (S[c][w r + k] = trunk[w][k C + c], utils/sample_shuffle.py:24-27).  So with
@@ -23,59 +24,47 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "stof_common.h"
+#include "train_ends.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
-constexpr int EC = 64;                      // num_features
-constexpr int ET_ROWS = 64;                 // rows per work-group of the element-wise kernels (4 passes of 16 rows)
-constexpr int EW_CHUNK = 256;               // rows per chunk of the weight-gradient kernels (16 passes of 16 rows)
+constexpr int EC = ENDS_C;                  // num_features
+constexpr int ET_ROWS = ENDS_TILE;          // rows per work-group of ed_out_dgrad_kernel
+constexpr int EW_CHUNK = ENDS_CHUNK;        // rows per chunk of the weight-gradient kernels
 constexpr int EW_MAX_COPIES = 1024;         // partials (work-groups) of a weight-gradient launch
-constexpr int ED_TILE = 256;                // outputs per work-group of ed_in_dgrad_kernel
-constexpr int64_t E_MAX_ROWS = (1ll << 25) - 1;      // N L 64 stays below 2^31
 
 inline bool r_ok(int32_t r) { return r >= 1 && r <= 64 && (r & (r - 1)) == 0; }
-// N L within the range of the 32-bit indices (N, L >= 1)
-inline bool rows_ok(int64_t N, int64_t L) { return N <= E_MAX_ROWS / L; }
 
-__device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ inline float4 masked_sum(const float* g, const float* g2, const float* saved, size_t at) {
-    float4 v = ld4(g + at);
-    if (g2) { const float4 u = ld4(g2 + at); v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w; }
-    const float4 s = ld4(saved + at);
-    return make_float4(s.x > 0.f ? v.x : 0.f, s.y > 0.f ? v.y : 0.f, s.z > 0.f ? v.z : 0.f, s.w > 0.f ? v.w : 0.f);
-}
+// conv_input's activation: ReLU; g' = (g + g2) * [saved > 0], g2 the long skip's gradient or NULL
+struct Relu {
+    static constexpr bool zero_fed_row_ends = true;
+    __device__ static float fwd(float v) { return fmaxf(v, 0.f); }
+    __device__ static float4 bwd(const float* g, const float* g2, const float* saved, size_t at) {
+        float4 v = ld4(g + at);
+        if (g2) { const float4 u = ld4(g2 + at); v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w; }
+        const float4 s = ld4(saved + at);
+        return make_float4(s.x > 0.f ? v.x : 0.f, s.y > 0.f ? v.y : 0.f, s.z > 0.f ? v.z : 0.f, s.w > 0.f ? v.w : 0.f);
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------- conv_input
-// Thread = (row slot tid >> 4, channels 4 q .. 4 q + 3): its twelve weights and four biases stay in registers for the four
-// rows it writes.  One output: bias, then taps 0..2 as one fmaf chain.
 __global__ __launch_bounds__(256) void ed_in_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                     float* __restrict__ y, int total, int L) {
-    const int q = threadIdx.x & 15, slot = threadIdx.x >> 4;
-    float wr[4][3], br[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        br[i] = b[4 * q + i];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) wr[i][d] = w[(4 * q + i) * 3 + d];
-    }
-    const int r0 = blockIdx.x * ET_ROWS + slot;
-    if (r0 >= total) return;
-    int t = r0 % L;
-#pragma unroll
-    for (int it = 0; it < ET_ROWS / 16; ++it) {
-        const int row = r0 + 16 * it;
-        if (row >= total) break;
-        const float xm = t > 0 ? x[row - 1] : 0.f, x0 = x[row], xp = t < L - 1 ? x[row + 1] : 0.f;
-        float o[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = fmaxf(fmaf(wr[i][2], xp, fmaf(wr[i][1], x0, fmaf(wr[i][0], xm, br[i]))), 0.f);
-        *reinterpret_cast<float4*>(y + (size_t)row * EC + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
-        t += 16;
-        if (t >= L) t %= L;
-    }
+    ends_in_fwd<3, Relu>(x, w, b, y, total, L);
+}
+__global__ __launch_bounds__(256) void ed_in_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ g,
+                                                          const float* __restrict__ g2, const float* __restrict__ saved,
+                                                          float* __restrict__ copies, int total, int L) {
+    ends_in_wgrad<3, Relu>(x, g, g2, saved, copies, total, L);
+}
+__global__ __launch_bounds__(256) void ed_in_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ g2,
+                                                          const float* __restrict__ saved, const float* __restrict__ w,
+                                                          float* __restrict__ dx, int total, int L, float out_scale) {
+    ends_in_dgrad<3, Relu>(g, g2, saved, w, dx, total, L, out_scale);
 }
 
-// Fold of a weight-gradient work-group: every thread holds 16 sums, [element i of its float4][tap 0..2 | plain sum]; the 16
+// Fold of ed_out_wgrad_kernel's work-group: every thread holds 16 sums, [element i of its float4][tap 0..2 | plain sum]; the 16
 // row slots are added pairwise in a fixed order -> fold[pos 0..63][4], pos = 4 q + i the float's position in its 64-float row.
 __device__ inline void fold_slots(float (&acc)[16], float* red, float* fold) {
     const int tid = threadIdx.x, q = tid & 15, slot = tid >> 4;
@@ -89,110 +78,6 @@ __device__ inline void fold_slots(float (&acc)[16], float* red, float* fold) {
         s[k] = (red[(4 * k) * 256 + tid] + red[(4 * k + 1) * 256 + tid]) + (red[(4 * k + 2) * 256 + tid] + red[(4 * k + 3) * 256 + tid]);
     fold[tid] = (s[0] + s[1]) + (s[2] + s[3]);
     __syncthreads();
-}
-
-// dw[f][d] = sum_rows g'[row][f] x[t + d - 1], db[f] = sum_rows g'[row][f].  Partial: [f * 3 + d] (192), then [192 + f].
-__global__ __launch_bounds__(256) void ed_in_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                          const float* __restrict__ g2, const float* __restrict__ saved,
-                                                          float* __restrict__ copies, int total, int L) {
-    __shared__ __attribute__((aligned(16))) float red[16 * 256];
-    __shared__ float fold[256];
-    const int tid = threadIdx.x, q = tid & 15, slot = tid >> 4;
-    float acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-    for (long long c0 = (long long)blockIdx.x * EW_CHUNK; c0 < total; c0 += (long long)gridDim.x * EW_CHUNK) {
-        const int r0 = (int)c0 + slot;
-        int t = r0 % L;
-#pragma unroll 4
-        for (int it = 0; it < EW_CHUNK / 16; ++it) {
-            const int row = r0 + 16 * it;
-            if (row >= total) break;
-            const float4 v = masked_sum(g, g2, saved, (size_t)row * EC + 4 * q);
-            const float xm = t > 0 ? x[row - 1] : 0.f, x0 = x[row], xp = t < L - 1 ? x[row + 1] : 0.f;
-            const float gv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                acc[4 * i] = fmaf(gv[i], xm, acc[4 * i]);
-                acc[4 * i + 1] = fmaf(gv[i], x0, acc[4 * i + 1]);
-                acc[4 * i + 2] = fmaf(gv[i], xp, acc[4 * i + 2]);
-                acc[4 * i + 3] += gv[i];
-            }
-            t += 16;
-            if (t >= L) t %= L;
-        }
-    }
-    fold_slots(acc, red, fold);
-    const int f = tid >> 2, d = tid & 3;
-    copies[(size_t)blockIdx.x * 256 + (d < 3 ? f * 3 + d : 192 + f)] = fold[tid];
-}
-
-// out[e] = out_scale * sum over the `ncopies` partials of E floats, element e < ndw -> dw[e], else db[e - ndw]: 64 elements x
-// 16 interleaved slices of the copies per work-group, four chains per slice, combined through LDS in a fixed order
-// (conv1_c_wgrad_reduce_kernel of widths.hip).
-__global__ __launch_bounds__(1024) void ed_wgrad_reduce_kernel(const float* __restrict__ copies, int ncopies, int stride, int E, int ndw,
-                                                               float* __restrict__ dw, float* __restrict__ db, float out_scale) {
-    __shared__ float red[16][64];
-    const int e = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + e;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (i < E) {
-        int k = sl;
-        for (; k + 48 < ncopies; k += 64) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] += copies[(size_t)(k + 16 * j) * stride + i];
-        }
-        for (; k < ncopies; k += 16) a[0] += copies[(size_t)k * stride + i];
-    }
-    red[sl][e] = (a[0] + a[1]) + (a[2] + a[3]);
-    __syncthreads();
-    if (sl != 0 || i >= E) return;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k += 4) s += (red[k][e] + red[k + 1][e]) + (red[k + 2][e] + red[k + 3][e]);
-    if (i < ndw) dw[i] = s * out_scale; else db[i - ndw] = s * out_scale;
-}
-
-// dx[row] = out_scale * (p1[row] + p0[row + 1] + p2[row - 1]) with p_d[row] = sum_f w[f][d] g'[row][f] (row ends: the neighbour's
-// term drops).  A work-group takes ED_TILE outputs: the 16 lanes of a row each form their four channels' share of the three
-// dot products, a fixed xor butterfly over the 16 lanes adds them, the 258 x 3 sums go through LDS.
-__global__ __launch_bounds__(256) void ed_in_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ g2,
-                                                          const float* __restrict__ saved, const float* __restrict__ w,
-                                                          float* __restrict__ dx, int total, int L, float out_scale) {
-    __shared__ float ps[3][ED_TILE + 2 + 14];              // [tap][row r0 - 1 + j], j < 258 (272 = 17 passes of 16 rows)
-    const int tid = threadIdx.x, q = tid & 15, slot = tid >> 4;
-    float wr[4][3];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) wr[i][d] = w[(4 * q + i) * 3 + d];
-    const long long r0 = (long long)blockIdx.x * ED_TILE;
-    for (int j = slot; j < ED_TILE + 2 + 14; j += 16) {      // (every lane of a wave stays in the loop: the butterfly needs all 16)
-        const long long row = r0 - 1 + j;
-        float p[3] = {0.f, 0.f, 0.f};
-        if (j < ED_TILE + 2 && row >= 0 && row < total) {
-            const float4 v = masked_sum(g, g2, saved, (size_t)row * EC + 4 * q);
-            const float gv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) p[d] = fmaf(wr[i][d], gv[i], p[d]);
-        }
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-#pragma unroll
-            for (int m = 8; m >= 1; m >>= 1) p[d] += __shfl_xor(p[d], m, 16);
-        }
-        if (q == 0) { ps[0][j] = p[0]; ps[1][j] = p[1]; ps[2][j] = p[2]; }
-    }
-    __syncthreads();
-    const long long row = r0 + tid;
-    if (row >= total) return;
-    const int t = (int)(row % L), j = tid + 1;
-    float s = ps[1][j];
-    if (t < L - 1) s += ps[0][j + 1];
-    if (t > 0) s += ps[2][j - 1];
-    dx[row] = s * out_scale;
 }
 
 // --------------------------------------------------------------------------------------- shuffle + conv_output
@@ -316,13 +201,7 @@ __global__ __launch_bounds__(256) void ed_out_wgrad_kernel(const float* __restri
     }
 }
 
-inline int wgrad_copies(int64_t rows) {
-    const int64_t chunks = (rows + EW_CHUNK - 1) / EW_CHUNK;
-    return (int)(chunks < EW_MAX_COPIES ? chunks : EW_MAX_COPIES);
-}
-constexpr size_t EW_WORKSPACE = (size_t)EW_MAX_COPIES * 256 * sizeof(float);
-
-inline int launched() { return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP; }
+constexpr size_t EW_WORKSPACE = (size_t)EW_MAX_COPIES * 256 * sizeof(float);       // a partial of either weight gradient: <= 256 floats
 
 #define ED_BY_R(KERNEL, r, ...)                                                          \
     switch (r) {                                                                         \
@@ -338,13 +217,11 @@ inline int launched() { return hipGetLastError() == hipSuccess ? STOF_OK : STOF_
 }  // namespace
 
 extern "C" int stof_train_edsr_in(const float* x, const float* w, const float* b, float* y, int64_t N, int64_t L, void* stream) {
-    if (N < 0 || L < 0) return STOF_ERR_BAD_ARG;
-    if (N == 0 || L == 0) return STOF_OK;
-    if (!x || !w || !b || !y) return STOF_ERR_BAD_ARG;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int rc = check_rows(N, L, x, w, b, y);
+    if (rc != ENDS_GO) return rc;
     const int total = (int)(N * L);
-    hipLaunchKernelGGL(ed_in_kernel, dim3((unsigned)((total + ET_ROWS - 1) / ET_ROWS)), dim3(256), 0, static_cast<hipStream_t>(stream), x, w,
-                       b, y, total, (int)L);
+    hipLaunchKernelGGL(ed_in_kernel, dim3((unsigned)((total + ENDS_TILE - 1) / ENDS_TILE)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                       w, b, y, total, (int)L);
     return launched();
 }
 
@@ -352,42 +229,32 @@ extern "C" size_t stof_train_edsr_in_wgrad_workspace_bytes(void) { return EW_WOR
 
 extern "C" int stof_train_edsr_in_wgrad(const float* x, const float* g, const float* g2, const float* saved, float* dw, float* db,
                                         int64_t N, int64_t L, float out_scale, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N < 0 || L < 0 || !dw || !db) return STOF_ERR_BAD_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (N == 0 || L == 0) {
-        if (hipMemsetAsync(dw, 0, EC * 3 * sizeof(float), s) != hipSuccess || hipMemsetAsync(db, 0, EC * sizeof(float), s) != hipSuccess)
-            return STOF_ERR_HIP;
-        return STOF_OK;
-    }
-    if (!x || !g || !saved || !workspace) return STOF_ERR_BAD_ARG;
-    if (workspace_bytes < EW_WORKSPACE) return STOF_ERR_WORKSPACE;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int rc = check_wgrad_rows(N, L, dw, EC * 3, db, EC, workspace_bytes, EW_WORKSPACE, s, x, g, saved, workspace);
+    if (rc != ENDS_GO) return rc;
     float* copies = static_cast<float*>(workspace);
-    const int gx = wgrad_copies(N * L);
+    const int gx = wgrad_copies(N * L, EW_CHUNK, EW_MAX_COPIES);
     hipLaunchKernelGGL(ed_in_wgrad_kernel, dim3((unsigned)gx), dim3(256), 0, s, x, g, g2, saved, copies, (int)(N * L), (int)L);
     if (launched() != STOF_OK) return STOF_ERR_HIP;
-    hipLaunchKernelGGL(ed_wgrad_reduce_kernel, dim3(4), dim3(1024), 0, s, copies, gx, 256, 256, 192, dw, db, out_scale);
+    partial_reduce(s, copies, gx, 256, 256, DwThenDb{dw, db, 192}, out_scale);
     return launched();
 }
 
 extern "C" int stof_train_edsr_in_dgrad(const float* g, const float* g2, const float* saved, const float* w, float* dx, int64_t N, int64_t L,
                                         float out_scale, void* stream) {
-    if (N < 0 || L < 0) return STOF_ERR_BAD_ARG;
-    if (N == 0 || L == 0) return STOF_OK;
-    if (!g || !saved || !w || !dx) return STOF_ERR_BAD_ARG;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int rc = check_rows(N, L, g, saved, w, dx);
+    if (rc != ENDS_GO) return rc;
     const int total = (int)(N * L);
-    hipLaunchKernelGGL(ed_in_dgrad_kernel, dim3((unsigned)((total + ED_TILE - 1) / ED_TILE)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       g, g2, saved, w, dx, total, (int)L, out_scale);
+    hipLaunchKernelGGL(ed_in_dgrad_kernel, dim3((unsigned)((total + ENDS_DTILE - 1) / ENDS_DTILE)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), g, g2, saved, w, dx, total, (int)L, out_scale);
     return launched();
 }
 
 extern "C" int stof_train_edsr_out(const float* trunk, const float* w, const float* b, float* y, int64_t N, int64_t L, int32_t r,
                                    void* stream) {
-    if (N < 0 || L < 0 || !r_ok(r)) return STOF_ERR_BAD_ARG;
-    if (N == 0 || L == 0) return STOF_OK;
-    if (!trunk || !w || !b || !y) return STOF_ERR_BAD_ARG;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    if (!r_ok(r)) return STOF_ERR_BAD_ARG;
+    const int rc = check_rows(N, L, trunk, w, b, y);
+    if (rc != ENDS_GO) return rc;
     const long long total = N * L * r;
     ED_BY_R(ed_out_kernel, r, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), trunk, w, b, y, total,
             (int)(L * r));
@@ -395,10 +262,9 @@ extern "C" int stof_train_edsr_out(const float* trunk, const float* w, const flo
 }
 
 extern "C" int stof_train_edsr_out_dgrad(const float* dy, const float* w, float* dtrunk, int64_t N, int64_t L, int32_t r, void* stream) {
-    if (N < 0 || L < 0 || !r_ok(r)) return STOF_ERR_BAD_ARG;
-    if (N == 0 || L == 0) return STOF_OK;
-    if (!dy || !w || !dtrunk) return STOF_ERR_BAD_ARG;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    if (!r_ok(r)) return STOF_ERR_BAD_ARG;
+    const int rc = check_rows(N, L, dy, w, dtrunk);
+    if (rc != ENDS_GO) return rc;
     const int total = (int)(N * L);
     ED_BY_R(ed_out_dgrad_kernel, r, dim3((unsigned)((total + ET_ROWS - 1) / ET_ROWS)), dim3(256), 0, static_cast<hipStream_t>(stream), dy, w,
             dtrunk, total, (int)L);
@@ -409,22 +275,15 @@ extern "C" size_t stof_train_edsr_out_wgrad_workspace_bytes(int32_t r) { return 
 
 extern "C" int stof_train_edsr_out_wgrad(const float* trunk, const float* dy, float* dw, float* db, int64_t N, int64_t L, int32_t r,
                                          float out_scale, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N < 0 || L < 0 || !r_ok(r) || !dw || !db) return STOF_ERR_BAD_ARG;
+    if (!r_ok(r)) return STOF_ERR_BAD_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int cq = EC / r;
-    if (N == 0 || L == 0) {
-        if (hipMemsetAsync(dw, 0, (size_t)cq * 3 * sizeof(float), s) != hipSuccess || hipMemsetAsync(db, 0, sizeof(float), s) != hipSuccess)
-            return STOF_ERR_HIP;
-        return STOF_OK;
-    }
-    if (!trunk || !dy || !workspace) return STOF_ERR_BAD_ARG;
-    if (workspace_bytes < EW_WORKSPACE) return STOF_ERR_WORKSPACE;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int rc = check_wgrad_rows(N, L, dw, (size_t)cq * 3, db, 1, workspace_bytes, EW_WORKSPACE, s, trunk, dy, workspace);
+    if (rc != ENDS_GO) return rc;
     float* copies = static_cast<float*>(workspace);
-    const int gx = wgrad_copies(N * L);
+    const int gx = wgrad_copies(N * L, EW_CHUNK, EW_MAX_COPIES);
     ED_BY_R(ed_out_wgrad_kernel, r, dim3((unsigned)gx), dim3(256), 0, s, trunk, dy, copies, (int)(N * L), (int)L);
     if (launched() != STOF_OK) return STOF_ERR_HIP;
-    hipLaunchKernelGGL(ed_wgrad_reduce_kernel, dim3((unsigned)((3 * cq + 1 + 63) / 64)), dim3(1024), 0, s, copies, gx, 256, 3 * cq + 1, 3 * cq,
-                       dw, db, out_scale);
+    partial_reduce(s, copies, gx, 256, 3 * cq + 1, DwThenDb{dw, db, 3 * cq}, out_scale);
     return launched();
 }

@@ -10,7 +10,8 @@
 //   ep_out_dgrad_kernel   g2 [N][L][32] = conv3^T(dz) (1 - h2^2)
 //   ep_in_wgrad_kernel    dW1 (64,1,5), db1 (64) from g' = g1 (1 - h1^2) and x
 //   ep_in_dgrad_kernel    dx [N][L] = conv1^T(g')
-//   ep_wgrad_reduce_kernel  the fixed-order sum over the partials of either weight gradient
+// conv1's three kernels are the shared input end of train_ends.h (K = 5, tanh); the partials of either weight gradient are added
+// by partial_reduce_kernel of wgrad_reduce.h.
 //
 // conv2's two gradient GEMMs are stof_train_wgrad(h1, g2) and stof_train_conv(g2, flipped W2) of train.hip: tanh' of conv2's
 // output is already in g2.
@@ -26,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "stof_common.h"
+#include "train_ends.h"
+#include "wgrad_reduce.h"
 #include "mfma32_frag.h"
 
 namespace {
@@ -33,70 +36,44 @@ namespace {
 using stof_frag::f32x16;
 
 constexpr int C1 = 64, C2 = 32;             // channels of h1, h2
-constexpr int PT_ROWS = 64;                 // rows per work-group of ep_in_kernel and ep_out_dgrad_kernel
+constexpr int PT_ROWS = ENDS_TILE;          // rows per work-group of ep_out_dgrad_kernel
 constexpr int PM_TILE = 128;                // rows per work-group of ep_mid_kernel (4 waves x 32 rows)
 constexpr int PM_STRIDE = 68;               // LDS row stride of its h1 tile (floats): 16 lanes of a ds_read_b128 on 16 slots
 constexpr int PM_GROUPS = 3 * C1 / 8;       // K groups of conv2: k = tap * 64 + ci, 8 per group
 constexpr int PO_OUTS = 2048;               // outputs per work-group of ep_out_kernel (8 passes of 256)
 constexpr int PO_WS = 100;                  // LDS stride of one output channel's 96 conv3 weights
-constexpr int PW_CHUNK = 256;               // rows per chunk of the weight-gradient kernels
+constexpr int PW_CHUNK = ENDS_CHUNK;        // rows per chunk of the weight-gradient kernels
 constexpr int PW_SUB = 64;                  // rows per LDS stage of ep_out_wgrad_kernel
 constexpr int PW_MAX_COPIES = 512;          // partials (work-groups) of a weight-gradient launch
-constexpr int PW_IN_E = C1 * 5 + C1;        // floats of a conv1 partial: dw [f * 5 + d], then db [320 + f]
-constexpr int PD_TILE = 256;                // outputs per work-group of ep_in_dgrad_kernel
-constexpr int PD_ROWS = PD_TILE + 4 + 12;   // its tile with the 2-row halos, as 17 passes of 16 rows
-constexpr int64_t P_MAX_ROWS = (1ll << 25) - 1;      // N L 64 stays below 2^31
+constexpr int PW_IN_E = ends_wgrad_floats<5>();      // floats of a conv1 partial: dw [f * 5 + d], then db [320 + f]
 
 inline bool r_ok(int32_t r) { return r >= 1 && r <= 64; }
-// N L within the range of the 32-bit indices (N, L >= 1)
-inline bool rows_ok(int64_t N, int64_t L) { return N <= P_MAX_ROWS / L; }
 __host__ __device__ inline int out_e(int r) { return r * (3 * C2 + 1); }                      // floats of a conv3 partial: dw, then db [r * 96 + j]
 
-__device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 // g (1 - s^2): the gradient through tanh, from the saved activation
 __device__ inline float4 tanh_bwd(float4 g, float4 s) {
     return make_float4(g.x * fmaf(-s.x, s.x, 1.f), g.y * fmaf(-s.y, s.y, 1.f), g.z * fmaf(-s.z, s.z, 1.f), g.w * fmaf(-s.w, s.w, 1.f));
 }
 
+// conv1's activation: tanh; g' = g (1 - saved^2)
+struct Tanh {
+    static constexpr bool zero_fed_row_ends = false;
+    __device__ static float fwd(float v) { return tanhf(v); }
+    __device__ static float4 bwd(const float* g, const float*, const float* saved, size_t at) { return tanh_bwd(ld4(g + at), ld4(saved + at)); }
+};
+
 // ------------------------------------------------------------------------------------------------------------- conv1
-// Thread = (row slot tid >> 4, channels 4 q .. 4 q + 3): its twenty weights and four biases stay in registers for the four
-// rows it writes.  One output: bias, then taps 0..4 as one fmaf chain; a tap that leaves the waveform is skipped.
 __global__ __launch_bounds__(256) void ep_in_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                     float* __restrict__ h1, int total, int L) {
-    const int q = threadIdx.x & 15, slot = threadIdx.x >> 4;
-    float wr[4][5], br[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        br[i] = b[4 * q + i];
-#pragma unroll
-        for (int d = 0; d < 5; ++d) wr[i][d] = w[(4 * q + i) * 5 + d];
-    }
-    const int r0 = blockIdx.x * PT_ROWS + slot;
-    if (r0 >= total) return;
-    int t = r0 % L;
-#pragma unroll
-    for (int it = 0; it < PT_ROWS / 16; ++it) {
-        const int row = r0 + 16 * it;
-        if (row >= total) break;
-        float xv[5];
-        bool ok[5];
-#pragma unroll
-        for (int d = 0; d < 5; ++d) {
-            ok[d] = t + d - 2 >= 0 && t + d - 2 < L;
-            xv[d] = ok[d] ? x[row + d - 2] : 0.f;
-        }
-        float o[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float acc = br[i];
-#pragma unroll
-            for (int d = 0; d < 5; ++d) acc = ok[d] ? fmaf(wr[i][d], xv[d], acc) : acc;
-            o[i] = tanhf(acc);
-        }
-        *reinterpret_cast<float4*>(h1 + (size_t)row * C1 + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
-        t += 16;
-        if (t >= L) t %= L;
-    }
+    ends_in_fwd<5, Tanh>(x, w, b, h1, total, L);
+}
+__global__ __launch_bounds__(256) void ep_in_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ h1,
+                                                          float* __restrict__ copies, int total, int L) {
+    ends_in_wgrad<5, Tanh>(x, g, nullptr, h1, copies, total, L);
+}
+__global__ __launch_bounds__(256) void ep_in_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ h1, const float* __restrict__ w,
+                                                          float* __restrict__ dx, int total, int L, float out_scale) {
+    ends_in_dgrad<5, Tanh>(g, nullptr, h1, w, dx, total, L, out_scale);
 }
 
 // ------------------------------------------------------------------------------------------------------------- conv2
@@ -342,139 +319,8 @@ __global__ __launch_bounds__(256) void ep_out_wgrad_kernel(const float* __restri
     }
 }
 
-// out[e] = out_scale * sum over the `ncopies` partials of E floats, element e < ndw -> dw[e], else db[e - ndw]: 64 elements x
-// 16 interleaved slices of the copies per work-group, four chains per slice, combined through LDS in a fixed order (the
-// scheme of ed_wgrad_reduce_kernel of edsr_train.hip).
-__global__ __launch_bounds__(1024) void ep_wgrad_reduce_kernel(const float* __restrict__ copies, int ncopies, int stride, int E, int ndw,
-                                                               float* __restrict__ dw, float* __restrict__ db, float out_scale) {
-    __shared__ float red[16][64];
-    const int e = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + e;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (i < E) {
-        int k = sl;
-        for (; k + 48 < ncopies; k += 64) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] += copies[(size_t)(k + 16 * j) * stride + i];
-        }
-        for (; k < ncopies; k += 16) a[0] += copies[(size_t)k * stride + i];
-    }
-    red[sl][e] = (a[0] + a[1]) + (a[2] + a[3]);
-    __syncthreads();
-    if (sl != 0 || i >= E) return;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k += 4) s += (red[k][e] + red[k + 1][e]) + (red[k + 2][e] + red[k + 3][e]);
-    if (i < ndw) dw[i] = s * out_scale; else db[i - ndw] = s * out_scale;
-}
-
-// ------------------------------------------------------------------------------------------------- conv1, backward
-// dw[f][d] = sum_rows g'[row][f] x[t + d - 2], db[f] = sum_rows g'[row][f].  Thread = (row slot tid >> 4, channels 4 q .. + 3)
-// with 24 sums [channel i][tap 0..4 | plain sum]; the 16 row slots are added pairwise in a fixed order through LDS.
-__global__ __launch_bounds__(256) void ep_in_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ h1,
-                                                          float* __restrict__ copies, int total, int L) {
-    __shared__ float red[16 * PW_IN_E];
-    const int tid = threadIdx.x, q = tid & 15, slot = tid >> 4;
-    float acc[4][6];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) acc[i][k] = 0.f;
-    for (long long c0 = (long long)blockIdx.x * PW_CHUNK; c0 < total; c0 += (long long)gridDim.x * PW_CHUNK) {
-        const int r0 = (int)c0 + slot;
-        int t = r0 % L;
-#pragma unroll 4
-        for (int it = 0; it < PW_CHUNK / 16; ++it) {
-            const int row = r0 + 16 * it;
-            if (row >= total) break;
-            const size_t at = (size_t)row * C1 + 4 * q;
-            const float4 v = tanh_bwd(ld4(g + at), ld4(h1 + at));
-            const float gv[4] = {v.x, v.y, v.z, v.w};
-            float xv[5];
-#pragma unroll
-            for (int d = 0; d < 5; ++d) xv[d] = (t + d - 2 >= 0 && t + d - 2 < L) ? x[row + d - 2] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                for (int d = 0; d < 5; ++d) acc[i][d] = fmaf(gv[i], xv[d], acc[i][d]);
-                acc[i][5] += gv[i];
-            }
-            t += 16;
-            if (t >= L) t %= L;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) red[slot * PW_IN_E + q * 24 + i * 6 + k] = acc[i][k];
-    __syncthreads();
-    for (int el = tid; el < PW_IN_E; el += 256) {
-        float s[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            s[k] = (red[(4 * k) * PW_IN_E + el] + red[(4 * k + 1) * PW_IN_E + el]) +
-                   (red[(4 * k + 2) * PW_IN_E + el] + red[(4 * k + 3) * PW_IN_E + el]);
-        const int f = 4 * (el / 24) + (el % 24) / 6, k = el % 6;
-        copies[(size_t)blockIdx.x * PW_IN_E + (k < 5 ? f * 5 + k : C1 * 5 + f)] = (s[0] + s[1]) + (s[2] + s[3]);
-    }
-}
-
-// dx[row] = out_scale * sum_d p_d[row - d + 2] with p_d[row] = sum_f w[f][d] g'[row][f], a term dropped where row - d + 2 leaves
-// the waveform; the terms are added in the order d = 2, 1, 3, 0, 4.  A work-group takes PD_TILE outputs: the 16 lanes of a
-// row each form their four channels' share of the five dot products, a fixed xor butterfly over the 16 lanes adds them, the
-// 260 x 5 sums go through LDS.
-__global__ __launch_bounds__(256) void ep_in_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ h1, const float* __restrict__ w,
-                                                          float* __restrict__ dx, int total, int L, float out_scale) {
-    __shared__ float ps[5][PD_ROWS];                         // [tap][row r0 - 2 + j], j < 260
-    const int tid = threadIdx.x, q = tid & 15, slot = tid >> 4;
-    float wr[4][5];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int d = 0; d < 5; ++d) wr[i][d] = w[(4 * q + i) * 5 + d];
-    const long long r0 = (long long)blockIdx.x * PD_TILE;
-    for (int j = slot; j < PD_ROWS; j += 16) {               // (every lane of a wave stays in the loop: the butterfly needs all 16)
-        const long long row = r0 - 2 + j;
-        float p[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        if (j < PD_TILE + 4 && row >= 0 && row < total) {
-            const size_t at = (size_t)row * C1 + 4 * q;
-            const float4 v = tanh_bwd(ld4(g + at), ld4(h1 + at));
-            const float gv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int d = 0; d < 5; ++d)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) p[d] = fmaf(wr[i][d], gv[i], p[d]);
-        }
-#pragma unroll
-        for (int d = 0; d < 5; ++d) {
-#pragma unroll
-            for (int m = 8; m >= 1; m >>= 1) p[d] += __shfl_xor(p[d], m, 16);
-        }
-        if (q == 0) {
-#pragma unroll
-            for (int d = 0; d < 5; ++d) ps[d][j] = p[d];
-        }
-    }
-    __syncthreads();
-    const long long row = r0 + tid;
-    if (row >= total) return;
-    const int t = (int)(row % L), j = tid + 2;
-    float s = ps[2][j];
-    if (t + 1 < L) s += ps[1][j + 1];
-    if (t >= 1) s += ps[3][j - 1];
-    if (t + 2 < L) s += ps[0][j + 2];
-    if (t >= 2) s += ps[4][j - 2];
-    dx[row] = s * out_scale;
-}
-
-inline int wgrad_copies(int64_t rows) {
-    const int64_t chunks = (rows + PW_CHUNK - 1) / PW_CHUNK;
-    return (int)(chunks < PW_MAX_COPIES ? chunks : PW_MAX_COPIES);
-}
 constexpr size_t PW_IN_WORKSPACE = (size_t)PW_MAX_COPIES * PW_IN_E * sizeof(float);
 inline size_t out_workspace(int r) { return (size_t)PW_MAX_COPIES * out_e(r) * sizeof(float); }
-
-inline int launched() { return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP; }
 
 }  // namespace
 
@@ -487,21 +333,17 @@ extern "C" int stof_train_espcn_repack(const float* w2, float* out, void* stream
 }
 
 extern "C" int stof_train_espcn_in(const float* x, const float* w, const float* b, float* h1, int64_t N, int64_t L, void* stream) {
-    if (N < 0 || L < 0) return STOF_ERR_BAD_ARG;
-    if (N == 0 || L == 0) return STOF_OK;
-    if (!x || !w || !b || !h1) return STOF_ERR_BAD_ARG;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int rc = check_rows(N, L, x, w, b, h1);
+    if (rc != ENDS_GO) return rc;
     const int total = (int)(N * L);
-    hipLaunchKernelGGL(ep_in_kernel, dim3((unsigned)((total + PT_ROWS - 1) / PT_ROWS)), dim3(256), 0, static_cast<hipStream_t>(stream), x, w,
-                       b, h1, total, (int)L);
+    hipLaunchKernelGGL(ep_in_kernel, dim3((unsigned)((total + ENDS_TILE - 1) / ENDS_TILE)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                       w, b, h1, total, (int)L);
     return launched();
 }
 
 extern "C" int stof_train_espcn_mid(const float* h1, const float* frag2, const float* b2, float* h2, int64_t N, int64_t L, void* stream) {
-    if (N < 0 || L < 0) return STOF_ERR_BAD_ARG;
-    if (N == 0 || L == 0) return STOF_OK;
-    if (!h1 || !frag2 || !b2 || !h2) return STOF_ERR_BAD_ARG;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int rc = check_rows(N, L, h1, frag2, b2, h2);
+    if (rc != ENDS_GO) return rc;
     const int total = (int)(N * L);
     hipLaunchKernelGGL(ep_mid_kernel, dim3((unsigned)((total + PM_TILE - 1) / PM_TILE)), dim3(256), 0, static_cast<hipStream_t>(stream), h1,
                        reinterpret_cast<const float4*>(frag2), b2, h2, total, (int)L);
@@ -510,10 +352,9 @@ extern "C" int stof_train_espcn_mid(const float* h1, const float* frag2, const f
 
 extern "C" int stof_train_espcn_out(const float* h2, const float* w, const float* b, float* y, int64_t N, int64_t L, int32_t r,
                                     void* stream) {
-    if (N < 0 || L < 0 || !r_ok(r)) return STOF_ERR_BAD_ARG;
-    if (N == 0 || L == 0) return STOF_OK;
-    if (!h2 || !w || !b || !y) return STOF_ERR_BAD_ARG;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    if (!r_ok(r)) return STOF_ERR_BAD_ARG;
+    const int rc = check_rows(N, L, h2, w, b, y);
+    if (rc != ENDS_GO) return rc;
     const long long total = N * L * r;
     hipLaunchKernelGGL(ep_out_kernel, dim3((unsigned)((total + PO_OUTS - 1) / PO_OUTS)), dim3(256), 0, static_cast<hipStream_t>(stream), h2, w,
                        b, y, (int)total, (int)L, (int)r);
@@ -524,35 +365,26 @@ extern "C" size_t stof_train_espcn_out_wgrad_workspace_bytes(int32_t r) { return
 
 extern "C" int stof_train_espcn_out_wgrad(const float* h2, const float* y, const float* dy, float* dw, float* db, int64_t N, int64_t L,
                                           int32_t r, float out_scale, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N < 0 || L < 0 || !r_ok(r) || !dw || !db) return STOF_ERR_BAD_ARG;
+    if (!r_ok(r)) return STOF_ERR_BAD_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (N == 0 || L == 0) {
-        if (hipMemsetAsync(dw, 0, (size_t)r * C2 * 3 * sizeof(float), s) != hipSuccess ||
-            hipMemsetAsync(db, 0, (size_t)r * sizeof(float), s) != hipSuccess)
-            return STOF_ERR_HIP;
-        return STOF_OK;
-    }
-    if (!h2 || !y || !dy || !workspace) return STOF_ERR_BAD_ARG;
-    if (workspace_bytes < out_workspace(r)) return STOF_ERR_WORKSPACE;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int rc = check_wgrad_rows(N, L, dw, (size_t)r * C2 * 3, db, (size_t)r, workspace_bytes, out_workspace(r), s, h2, y, dy, workspace);
+    if (rc != ENDS_GO) return rc;
     float* copies = static_cast<float*>(workspace);
-    const int gx = wgrad_copies(N * L);
+    const int gx = wgrad_copies(N * L, PW_CHUNK, PW_MAX_COPIES);
     int js_log2 = 0;
     while ((1 << js_log2) < r && js_log2 < 5) ++js_log2;
     hipLaunchKernelGGL(ep_out_wgrad_kernel, dim3((unsigned)gx), dim3(256), 0, s, h2, y, dy, copies, (int)(N * L), (int)L, (int)r, js_log2);
     if (launched() != STOF_OK) return STOF_ERR_HIP;
     const int E = out_e(r);
-    hipLaunchKernelGGL(ep_wgrad_reduce_kernel, dim3((unsigned)((E + 63) / 64)), dim3(1024), 0, s, copies, gx, E, E, r * 3 * C2, dw, db,
-                       out_scale);
+    partial_reduce(s, copies, gx, E, E, DwThenDb{dw, db, r * 3 * C2}, out_scale);
     return launched();
 }
 
 extern "C" int stof_train_espcn_out_dgrad(const float* y, const float* dy, const float* h2, const float* w, float* g2, int64_t N, int64_t L,
                                           int32_t r, void* stream) {
-    if (N < 0 || L < 0 || !r_ok(r)) return STOF_ERR_BAD_ARG;
-    if (N == 0 || L == 0) return STOF_OK;
-    if (!y || !dy || !h2 || !w || !g2) return STOF_ERR_BAD_ARG;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    if (!r_ok(r)) return STOF_ERR_BAD_ARG;
+    const int rc = check_rows(N, L, y, dy, h2, w, g2);
+    if (rc != ENDS_GO) return rc;
     const int total = (int)(N * L);
     hipLaunchKernelGGL(ep_out_dgrad_kernel, dim3((unsigned)((total + PT_ROWS - 1) / PT_ROWS)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        y, dy, h2, w, g2, total, (int)L, (int)r);
@@ -563,32 +395,23 @@ extern "C" size_t stof_train_espcn_in_wgrad_workspace_bytes(void) { return PW_IN
 
 extern "C" int stof_train_espcn_in_wgrad(const float* x, const float* g1, const float* h1, float* dw, float* db, int64_t N, int64_t L,
                                          float out_scale, void* workspace, size_t workspace_bytes, void* stream) {
-    if (N < 0 || L < 0 || !dw || !db) return STOF_ERR_BAD_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (N == 0 || L == 0) {
-        if (hipMemsetAsync(dw, 0, C1 * 5 * sizeof(float), s) != hipSuccess || hipMemsetAsync(db, 0, C1 * sizeof(float), s) != hipSuccess)
-            return STOF_ERR_HIP;
-        return STOF_OK;
-    }
-    if (!x || !g1 || !h1 || !workspace) return STOF_ERR_BAD_ARG;
-    if (workspace_bytes < PW_IN_WORKSPACE) return STOF_ERR_WORKSPACE;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int rc = check_wgrad_rows(N, L, dw, C1 * 5, db, C1, workspace_bytes, PW_IN_WORKSPACE, s, x, g1, h1, workspace);
+    if (rc != ENDS_GO) return rc;
     float* copies = static_cast<float*>(workspace);
-    const int gx = wgrad_copies(N * L);
+    const int gx = wgrad_copies(N * L, PW_CHUNK, PW_MAX_COPIES);
     hipLaunchKernelGGL(ep_in_wgrad_kernel, dim3((unsigned)gx), dim3(256), 0, s, x, g1, h1, copies, (int)(N * L), (int)L);
     if (launched() != STOF_OK) return STOF_ERR_HIP;
-    hipLaunchKernelGGL(ep_wgrad_reduce_kernel, dim3(PW_IN_E / 64), dim3(1024), 0, s, copies, gx, PW_IN_E, PW_IN_E, C1 * 5, dw, db, out_scale);
+    partial_reduce(s, copies, gx, PW_IN_E, PW_IN_E, DwThenDb{dw, db, C1 * 5}, out_scale);
     return launched();
 }
 
 extern "C" int stof_train_espcn_in_dgrad(const float* g1, const float* h1, const float* w, float* dx, int64_t N, int64_t L, float out_scale,
                                          void* stream) {
-    if (N < 0 || L < 0) return STOF_ERR_BAD_ARG;
-    if (N == 0 || L == 0) return STOF_OK;
-    if (!g1 || !h1 || !w || !dx) return STOF_ERR_BAD_ARG;
-    if (!rows_ok(N, L)) return STOF_ERR_UNSUPPORTED;
+    const int rc = check_rows(N, L, g1, h1, w, dx);
+    if (rc != ENDS_GO) return rc;
     const int total = (int)(N * L);
-    hipLaunchKernelGGL(ep_in_dgrad_kernel, dim3((unsigned)((total + PD_TILE - 1) / PD_TILE)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       g1, h1, w, dx, total, (int)L, out_scale);
+    hipLaunchKernelGGL(ep_in_dgrad_kernel, dim3((unsigned)((total + ENDS_DTILE - 1) / ENDS_DTILE)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), g1, h1, w, dx, total, (int)L, out_scale);
     return launched();
 }

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include "stof_common.h"
 #include "stof_hip_util.h"
+#include "wgrad_reduce.h"
 
 using namespace stof;
 
@@ -1722,30 +1723,6 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const float* __restric
     }
 }
 
-// 640 sums over the partials, in a fixed order: 64 elements x 16 interleaved slices of the copies per work-group (one wave each, four
-// chains per wave so that loads stay in flight), combined through LDS
-__global__ __launch_bounds__(1024) void conv1_wgrad_reduce_kernel(const float* __restrict__ copies, int ncopies, float* __restrict__ dw,
-                                                                  float* __restrict__ db, float out_scale) {
-    __shared__ float red[16][64];
-    const int e = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + e;                            // (ch, d), 640 in all: 10 work-groups
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    int c = q;
-    for (; c + 48 < ncopies; c += 64) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] += copies[(size_t)(c + 16 * k) * 640 + i];
-    }
-    for (; c < ncopies; c += 16) a[0] += copies[(size_t)c * 640 + i];
-    red[q][e] = (a[0] + a[1]) + (a[2] + a[3]);
-    __syncthreads();
-    if (q != 0) return;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k += 4) s += (red[k][e] + red[k + 1][e]) + (red[k + 2][e] + red[k + 3][e]);
-    const int ch = i / 10, d = i - ch * 10;
-    if (d < 9) dw[ch * 9 + d] = s * out_scale; else db[ch] = s * out_scale;
-}
-
 // Gradient with respect to the input frame (models/stofnet.py:45 differentiated: the reference's autograd provides it for free):
 // dx[n][u] = out_scale * sum_d sum_ch w1[ch][d] g'[n][u + 4 - d][ch],  g' = g * relu'(saved conv1 output).  One thread per sample;
 // the nine rows of g' it reads are shared with its neighbours through the caches; off the hot path (nobody trains the input).
@@ -2355,7 +2332,7 @@ extern "C" int stof_train_conv1_wgrad(const float* x, const float* g, const floa
     const int64_t chunks = (N * L + C1_CHUNK - 1) / C1_CHUNK;
     const int grid = (int)(chunks < C1_COPIES ? chunks : C1_COPIES);
     hipLaunchKernelGGL(conv1_wgrad_kernel, dim3((unsigned)grid), dim3(256), 0, s, x, g, saved, copies, (int)N, (int)L);
-    hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(10), dim3(1024), 0, s, copies, grid, dw, db, out_scale);
+    partial_reduce(s, copies, grid, 640, 640, TapsThenBias{dw, db}, out_scale);        // 640 sums (ch, d) over the partials
     return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP;
 }
 

@@ -1,0 +1,82 @@
+// The second half of every weight gradient that is summed without float atomics: the work-groups of the first kernel each wrote
+// ONE partial of E floats (`copies`, `stride` floats apart), this kernel adds the `ncopies` partials of every element in an
+// order that depends on ncopies alone, so two runs are bitwise equal.  The order is part of the results' bits:
+//
+//   a work-group takes 64 elements x 16 interleaved slices of the partials (slice sl: k = sl, sl + 16, ...); a slice runs four
+//   chains while k + 48 < ncopies, the rest goes into chain 0, the chains fold as (a0 + a1) + (a2 + a3); the 16 slices then fold
+//   through LDS, four at a time in order: s += (r[k] + r[k + 1]) + (r[k + 2] + r[k + 3]).
+//
+// Where the sum of element i goes is the caller's `Map`: used(i) (false: a slot that no partial holds) and store(i, value).
+// (wgrad_reduce_kernel and sgb_wgrad_reduce_kernel of train.hip are a different scheme.)
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace {
+
+// elements 0 .. ndw - 1 are dw, the rest db
+struct DwThenDb {
+    float *dw, *db;
+    int ndw;
+    __device__ bool used(int) const { return true; }
+    __device__ void store(int i, float v) const {
+        if (i < ndw) dw[i] = v; else db[i - ndw] = v;
+    }
+};
+
+// ten per channel: nine taps -> dw (ch, 9), slot 9 -> db (ch)
+struct TapsThenBias {
+    float *dw, *db;
+    __device__ bool used(int) const { return true; }
+    __device__ void store(int i, float v) const {
+        const int ch = i / 10, d = i - ch * 10;
+        if (d < 9) dw[ch * 9 + d] = v; else db[ch] = v;
+    }
+};
+
+// ten per (f, c): nine taps -> dw (f, c, 9), slot 9 -> db (f) for c = 0; the bias slot of c > 0 is never written
+struct TapsThenBiasPerInput {
+    float *dw, *db;
+    int Cin;
+    __device__ bool used(int i) const {
+        const int fc = i / 10;
+        return i - fc * 10 < 9 || fc % Cin == 0;
+    }
+    __device__ void store(int i, float v) const {
+        const int fc = i / 10, d = i - fc * 10;
+        if (d < 9) dw[(size_t)fc * 9 + d] = v; else db[fc / Cin] = v;
+    }
+};
+
+template <class Map>
+__global__ __launch_bounds__(1024) void partial_reduce_kernel(const float* __restrict__ copies, int ncopies, int stride, int E, Map map,
+                                                              float out_scale) {
+    __shared__ float red[16][64];
+    const int e = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int i = blockIdx.x * 64 + e;
+    const bool used = i < E && map.used(i);
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    if (used) {
+        int k = sl;
+        for (; k + 48 < ncopies; k += 64) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] += copies[(size_t)(k + 16 * j) * stride + i];
+        }
+        for (; k < ncopies; k += 16) a[0] += copies[(size_t)k * stride + i];
+    }
+    red[sl][e] = (a[0] + a[1]) + (a[2] + a[3]);
+    __syncthreads();
+    if (sl != 0 || !used) return;
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; k += 4) s += (red[k][e] + red[k + 1][e]) + (red[k + 2][e] + red[k + 3][e]);
+    map.store(i, s * out_scale);
+}
+
+// one work-group per 64 elements
+template <class Map>
+inline void partial_reduce(hipStream_t s, const float* copies, int ncopies, int stride, int E, Map map, float out_scale) {
+    hipLaunchKernelGGL(partial_reduce_kernel<Map>, dim3((unsigned)((E + 63) / 64)), dim3(1024), 0, s, copies, ncopies, stride, E, map,
+                       out_scale);
+}
+
+}  // namespace

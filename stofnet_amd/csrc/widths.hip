@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "stof_common.h"
 #include "stof_hip_util.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
@@ -131,35 +132,6 @@ __global__ __launch_bounds__(256) void conv1_c_wgrad_kernel(const float* __restr
         }
     }
     if (c0 == 0) copy[(size_t)f * Cin * 10 + 9] = (red[0][ch][NA - 1] + red[1][ch][NA - 1]) + (red[2][ch][NA - 1] + red[3][ch][NA - 1]);
-}
-
-// The F x Cin x 10 sums over the partials, in a fixed order: 64 elements x 16 interleaved slices of the copies per work-group,
-// four chains per slice, combined through LDS (conv1_wgrad_reduce_kernel of train.hip for any element count).
-__global__ __launch_bounds__(1024) void conv1_c_wgrad_reduce_kernel(const float* __restrict__ copies, int ncopies, float* __restrict__ dw,
-                                                                    float* __restrict__ db, int Cin, int F, float out_scale) {
-    __shared__ float red[16][64];
-    const int e = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int E = F * Cin * 10;
-    const int i = blockIdx.x * 64 + e;
-    const int fc = i / 10, d = i - fc * 10;
-    const int f = fc / Cin, c = fc - f * Cin;
-    const bool used = i < E && (d < 9 || c == 0);                 // (the bias slot of c > 0 is never written)
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (used) {
-        int k = q;
-        for (; k + 48 < ncopies; k += 64) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] += copies[(size_t)(k + 16 * j) * E + i];
-        }
-        for (; k < ncopies; k += 16) a[0] += copies[(size_t)k * E + i];
-    }
-    red[q][e] = (a[0] + a[1]) + (a[2] + a[3]);
-    __syncthreads();
-    if (q != 0 || !used) return;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k += 4) s += (red[k][e] + red[k + 1][e]) + (red[k + 2][e] + red[k + 3][e]);
-    if (d < 9) dw[(size_t)fc * 9 + d] = s * out_scale; else db[f] = s * out_scale;
 }
 
 // dx[n][c][u] = out_scale * sum_f sum_d w[f][c][d] g'[n][u + 4 - d][f].  A work-group takes 64 samples of one waveform and walks
@@ -293,8 +265,8 @@ extern "C" int stof_train_conv1_c_wgrad(const float* x, const float* g, const fl
     if (cg == 1) hipLaunchKernelGGL(conv1_c_wgrad_kernel<1>, grid, dim3(256), 0, s, x, g, saved, copies, (int)N, (int)L, Cin, F);
     else if (cg == 2) hipLaunchKernelGGL(conv1_c_wgrad_kernel<2>, grid, dim3(256), 0, s, x, g, saved, copies, (int)N, (int)L, Cin, F);
     else hipLaunchKernelGGL(conv1_c_wgrad_kernel<4>, grid, dim3(256), 0, s, x, g, saved, copies, (int)N, (int)L, Cin, F);
-    hipLaunchKernelGGL(conv1_c_wgrad_reduce_kernel, dim3((unsigned)((F * Cin * 10 + 63) / 64)), dim3(1024), 0, s, copies, gx, dw, db, Cin, F,
-                       out_scale);
+    const int E = F * Cin * 10;                                   // the sums (f, c, d) over the partials
+    partial_reduce(s, copies, gx, E, E, TapsThenBiasPerInput{dw, db, Cin}, out_scale);
     return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP;
 }
 

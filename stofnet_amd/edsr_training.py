@@ -8,11 +8,11 @@ SampleShuffle1D(r) image, so the shuffle costs nothing in either direction.  No 
 give bitwise equal gradients."""
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
 from . import _lib
-from .training import ACT_NONE, ACT_RELU, LayerKernels
+from ._train_boundary import EndsFunction, SavedStepEngine
+from .training import ACT_NONE, ACT_RELU
 
 
 @dataclass
@@ -27,14 +27,14 @@ class EdsrSaved:
     trunk: torch.Tensor     # [N, L, 64] conv_mid + a0 = the input of `upscale`
 
 
-class EdsrTrainEngine(LayerKernels):
+class EdsrTrainEngine(SavedStepEngine):
     """Forward with saved activations and backward pass of EDSR_1D on explicit parameter / gradient dictionaries (the
     state_dict's names), mirroring `TrainEngine`."""
+    label = 'EDSR_1D'
 
     def __init__(self, dev, num_blocks, r):
-        super().__init__(dev, _lib.PREC_FP32)
-        self.B, self.r = int(num_blocks), int(r)
-        self._images = {}           # (layer name, flip) -> ((data_ptr, _version) of the weight, its kernel-layout image)
+        super().__init__(dev, r)
+        self.B = int(num_blocks)
 
     def body_layers(self):
         return [f'residual_blocks.{i}.conv{j}' for i in range(self.B) for j in (1, 2)] + ['conv_mid']
@@ -42,17 +42,12 @@ class EdsrTrainEngine(LayerKernels):
     def _image(self, p, name, flip):
         """Tap-major image of a 64 -> 64 weight (flip: the data-gradient operand), repacked when the parameter changed."""
         w = p[name + '.weight']
-        key = (w.data_ptr(), w._version)
-        hit = self._images.get((name, flip))
-        if hit is None or hit[0] != key:
-            hit = self._images[(name, flip)] = (key, self._repack(w.contiguous(), flip))
-        return hit[1]
+        return self._cached((name, flip), w, lambda: self._repack(w.contiguous(), flip))
 
     def _forward_saved(self, p, frame):
         """models/edsr_1d.py:38-45 -> (y [N, L r], EdsrSaved)."""
-        _lib.require_device(frame, 'frame')
         lib, st = _lib.lib(), self._st()
-        x = frame.detach().reshape(frame.shape[0], frame.shape[-1]).contiguous().float()
+        x = self._flat_frame(frame)
         n, L = x.shape
         p = {k: v.contiguous() for k, v in p.items()}
         fwd = {nm: self._image(p, nm, False) for nm in self.body_layers()}
@@ -77,12 +72,7 @@ class EdsrTrainEngine(LayerKernels):
         shape) and, if `dx` [N, L] is given, the gradient with respect to the input frame into it."""
         lib, st, p, r = _lib.lib(), self._st(), saved.p, self.r
         n, L = saved.x.shape
-        # the data gradients read the weights again (the flipped images are packed here, only when a backward runs): an
-        # in-place edit since the forward would be used silently, where torch's own convolutions raise
-        for k, v in p.items():
-            if v._version != saved.versions[k]:
-                raise RuntimeError(f'EDSR_1D: parameter {k} needed for gradient computation has been modified by an inplace '
-                                   f'operation (version {v._version}, expected {saved.versions[k]})')
+        self._check_versions(saved)
         bwd = {nm: self._image(p, nm, True) for nm in self.body_layers()}
         ws = self._scratch('_edsr_out_ws', lib.stof_train_edsr_out_wgrad_workspace_bytes(r))
         _lib.check(lib.stof_train_edsr_out_wgrad(_lib.ptr(saved.trunk), _lib.ptr(dy), _lib.ptr(g['conv_output.weight']),
@@ -108,37 +98,5 @@ class EdsrTrainEngine(LayerKernels):
                                                     _lib.ptr(dx), n, L, 1.0, st), 'stof_train_edsr_in_dgrad')
 
 
-class EdsrFunction(torch.autograd.Function):
-    """Autograd boundary of `EDSR_1D.forward_train_kernels`, on the pattern of `StofNetFunction`: `y = model(frame)` returns a
-    tensor whose `backward()` runs the gfx950 data- and weight-gradient kernels and hands torch the gradient of every
-    parameter (and of the frame, when it asks for one), so torch's loss, `optim.AdamW` and scheduler run unchanged."""
-
-    @staticmethod
-    def forward(ctx, frame, engine, names, *params):
-        n, L = int(frame.shape[0]), int(frame.shape[-1])
-        ctx.engine, ctx.names, ctx.shapes, ctx.dims = engine, names, [tuple(v.shape) for v in params], (n, L)
-        if n == 0 or L == 0:
-            ctx.saved = ()
-            return torch.empty((n, 1, L * engine.r), dtype=torch.float32, device=engine.dev)
-        with torch.cuda.device(engine.dev):
-            y, ctx.saved = engine._forward_saved({k: v.detach() for k, v in zip(names, params)}, frame)
-        return y.view(n, 1, L * engine.r)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        engine, saved, (n, L) = ctx.engine, ctx.saved, ctx.dims
-        if saved is None:
-            raise RuntimeError('Trying to backward through the graph a second time: the saved activations of '
-                               'EDSR_1D.forward have been freed')
-        with torch.cuda.device(engine.dev):
-            sizes = [int(np.prod(sh)) if len(sh) else 1 for sh in ctx.shapes]
-            flat = torch.zeros(sum(sizes), dtype=torch.float32, device=engine.dev)    # fresh: torch may keep these views as .grad
-            g, off = {}, 0
-            for name, sh, k in zip(ctx.names, ctx.shapes, sizes):
-                g[name] = flat[off:off + k].view(sh)
-                off += k
-            dx = torch.empty((n, L), dtype=torch.float32, device=engine.dev) if ctx.needs_input_grad[0] else None
-            if n and L:
-                engine._backward_saved(saved, grad_out.detach().reshape(n, L * engine.r).contiguous().float(), g, dx)
-        ctx.saved = None
-        return (None if dx is None else dx.view(n, 1, L), None, None) + tuple(g[name] for name in ctx.names)
+class EdsrFunction(EndsFunction):
+    """Autograd boundary of `EDSR_1D.forward_train_kernels`."""

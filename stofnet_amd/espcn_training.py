@@ -9,11 +9,10 @@ gradient (which apply tanh' of h1).  In channel-last order z [N][L][r] is its ow
 costs nothing in either direction.  No MIOpen call and no float atomic: two runs give bitwise equal gradients."""
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
 from . import _lib
-from .training import LayerKernels
+from ._train_boundary import EndsFunction, SavedStepEngine
 
 
 @dataclass
@@ -27,43 +26,31 @@ class EspcnSaved:
     y: torch.Tensor         # [N, L r] the output: sigmoid' = y (1 - y)
 
 
-class EspcnTrainEngine(LayerKernels):
+class EspcnTrainEngine(SavedStepEngine):
     """Forward with saved activations and backward pass of ESPCN_1D on explicit parameter / gradient dictionaries (the
     state_dict's names), mirroring `EdsrTrainEngine`."""
+    label = 'ESPCN_1D'
 
-    def __init__(self, dev, r):
-        super().__init__(dev, _lib.PREC_FP32)
-        self.r = int(r)
-        self._images = {}           # 'mid' | 'flip' -> ((data_ptr, _version) of conv2.weight, its kernel-layout image)
-
-    def _image(self, p, which):
-        """An image of conv2.weight, repacked on the device when the parameter changed: 'mid' = the MFMA operand of
-        `stof_train_espcn_mid`, 'flip' = the data-gradient operand of `stof_train_conv`."""
-        w = p['conv2.weight']
-        key = (w.data_ptr(), w._version)
-        hit = self._images.get(which)
-        if hit is None or hit[0] != key:
-            if which == 'flip':
-                img = self._repack(w, True)
-            else:
-                lib = _lib.lib()
-                img = torch.empty(lib.stof_train_espcn_repack_floats(), dtype=torch.float32, device=self.dev)
-                _lib.check(lib.stof_train_espcn_repack(_lib.ptr(w), _lib.ptr(img), self._st()), 'stof_train_espcn_repack')
-            hit = self._images[which] = (key, img)
-        return hit[1]
+    def _repack_mid(self, w):
+        """conv2.weight as the MFMA operand of `stof_train_espcn_mid`"""
+        lib = _lib.lib()
+        img = torch.empty(lib.stof_train_espcn_repack_floats(), dtype=torch.float32, device=self.dev)
+        _lib.check(lib.stof_train_espcn_repack(_lib.ptr(w), _lib.ptr(img), self._st()), 'stof_train_espcn_repack')
+        return img
 
     def _forward_saved(self, p, frame):
         """models/espcn_1d.py:31-36 -> (y [N, L r], EspcnSaved)."""
-        _lib.require_device(frame, 'frame')
         lib, st, r = _lib.lib(), self._st(), self.r
-        x = frame.detach().reshape(frame.shape[0], frame.shape[-1]).contiguous().float()
+        x = self._flat_frame(frame)
         n, L = x.shape
         p = {k: v.contiguous() for k, v in p.items()}
         h1 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
         _lib.check(lib.stof_train_espcn_in(_lib.ptr(x), _lib.ptr(p['conv1.weight']), _lib.ptr(p['conv1.bias']), _lib.ptr(h1), n, L, st),
                    'stof_train_espcn_in')
         h2 = torch.empty((n, L, 32), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_train_espcn_mid(_lib.ptr(h1), _lib.ptr(self._image(p, 'mid')), _lib.ptr(p['conv2.bias']), _lib.ptr(h2), n, L, st),
+        w2 = p['conv2.weight']
+        mid = self._cached('mid', w2, lambda: self._repack_mid(w2))
+        _lib.check(lib.stof_train_espcn_mid(_lib.ptr(h1), _lib.ptr(mid), _lib.ptr(p['conv2.bias']), _lib.ptr(h2), n, L, st),
                    'stof_train_espcn_mid')
         y = torch.empty((n, L * r), dtype=torch.float32, device=self.dev)
         _lib.check(lib.stof_train_espcn_out(_lib.ptr(h2), _lib.ptr(p['conv3.weight']), _lib.ptr(p['conv3.bias']), _lib.ptr(y), n, L, r, st),
@@ -75,12 +62,7 @@ class EspcnTrainEngine(LayerKernels):
         shape) and, if `dx` [N, L] is given, the gradient with respect to the input frame into it."""
         lib, st, p, r = _lib.lib(), self._st(), saved.p, self.r
         n, L = saved.x.shape
-        # the data gradients read the weights again: an in-place edit since the forward would be used silently, where torch's
-        # own convolutions raise
-        for k, v in p.items():
-            if v._version != saved.versions[k]:
-                raise RuntimeError(f'ESPCN_1D: parameter {k} needed for gradient computation has been modified by an inplace '
-                                   f'operation (version {v._version}, expected {saved.versions[k]})')
+        self._check_versions(saved)
         ws = self._scratch('_espcn_out_ws', lib.stof_train_espcn_out_wgrad_workspace_bytes(r))
         _lib.check(lib.stof_train_espcn_out_wgrad(_lib.ptr(saved.h2), _lib.ptr(saved.y), _lib.ptr(dy), _lib.ptr(g['conv3.weight']),
                                                   _lib.ptr(g['conv3.bias']), n, L, r, 1.0, _lib.ptr(ws), ws.numel(), st),
@@ -89,7 +71,9 @@ class EspcnTrainEngine(LayerKernels):
         _lib.check(lib.stof_train_espcn_out_dgrad(_lib.ptr(saved.y), _lib.ptr(dy), _lib.ptr(saved.h2), _lib.ptr(p['conv3.weight']),
                                                   _lib.ptr(g2), n, L, r, st), 'stof_train_espcn_out_dgrad')
         self._wgrad(saved.h1, g2, g['conv2.weight'], g['conv2.bias'], 64, 32, 3)
-        g1 = self._conv(g2, self._image(p, 'flip'), None, 32, 64, 3)                  # dloss/dh1: tanh' of h1 is applied by its readers
+        w2 = p['conv2.weight']
+        flip = self._cached('flip', w2, lambda: self._repack(w2, True))               # the data-gradient operand of `stof_train_conv`
+        g1 = self._conv(g2, flip, None, 32, 64, 3)                                    # dloss/dh1: tanh' of h1 is applied by its readers
         ws = self._scratch('_espcn_in_ws', lib.stof_train_espcn_in_wgrad_workspace_bytes())
         _lib.check(lib.stof_train_espcn_in_wgrad(_lib.ptr(saved.x), _lib.ptr(g1), _lib.ptr(saved.h1), _lib.ptr(g['conv1.weight']),
                                                  _lib.ptr(g['conv1.bias']), n, L, 1.0, _lib.ptr(ws), ws.numel(), st),
@@ -99,37 +83,5 @@ class EspcnTrainEngine(LayerKernels):
                                                      1.0, st), 'stof_train_espcn_in_dgrad')
 
 
-class EspcnFunction(torch.autograd.Function):
-    """Autograd boundary of `ESPCN_1D.forward_train_kernels`, on the pattern of `EdsrFunction`: `y = model(frame)` returns a
-    tensor whose `backward()` runs the gfx950 data- and weight-gradient kernels and hands torch the gradient of every
-    parameter (and of the frame, when it asks for one), so torch's loss, `optim.AdamW` and scheduler run unchanged."""
-
-    @staticmethod
-    def forward(ctx, frame, engine, names, *params):
-        n, L = int(frame.shape[0]), int(frame.shape[-1])
-        ctx.engine, ctx.names, ctx.shapes, ctx.dims = engine, names, [tuple(v.shape) for v in params], (n, L)
-        if n == 0 or L == 0:
-            ctx.saved = ()
-            return torch.empty((n, 1, L * engine.r), dtype=torch.float32, device=engine.dev)
-        with torch.cuda.device(engine.dev):
-            y, ctx.saved = engine._forward_saved({k: v.detach() for k, v in zip(names, params)}, frame)
-        return y.view(n, 1, L * engine.r)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        engine, saved, (n, L) = ctx.engine, ctx.saved, ctx.dims
-        if saved is None:
-            raise RuntimeError('Trying to backward through the graph a second time: the saved activations of '
-                               'ESPCN_1D.forward have been freed')
-        with torch.cuda.device(engine.dev):
-            sizes = [int(np.prod(sh)) if len(sh) else 1 for sh in ctx.shapes]
-            flat = torch.zeros(sum(sizes), dtype=torch.float32, device=engine.dev)    # fresh: torch may keep these views as .grad
-            g, off = {}, 0
-            for name, sh, k in zip(ctx.names, ctx.shapes, sizes):
-                g[name] = flat[off:off + k].view(sh)
-                off += k
-            dx = torch.empty((n, L), dtype=torch.float32, device=engine.dev) if ctx.needs_input_grad[0] else None
-            if n and L:
-                engine._backward_saved(saved, grad_out.detach().reshape(n, L * engine.r).contiguous().float(), g, dx)
-        ctx.saved = None
-        return (None if dx is None else dx.view(n, 1, L), None, None) + tuple(g[name] for name in ctx.names)
+class EspcnFunction(EndsFunction):
+    """Autograd boundary of `ESPCN_1D.forward_train_kernels`."""

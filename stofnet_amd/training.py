@@ -498,6 +498,7 @@ class StofNetFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
+        from ._train_boundary import carve_grads            # (that module builds on LayerKernels above)
         engine, saved = ctx.engine, ctx.saved
         if saved is None:
             raise RuntimeError('Trying to backward through the graph a second time: the saved activations of '
@@ -530,12 +531,7 @@ class StofNetFunction(torch.autograd.Function):
                 if amax > 0.0 and math.isfinite(amax):
                     gscale = 2.0 ** (-math.floor(math.log2(amax)))
                     dpred = dpred * gscale
-            sizes = [int(np.prod(sh)) if len(sh) else 1 for sh in ctx.shapes]
-            flat = torch.zeros(sum(sizes), dtype=torch.float32, device=engine.dev)    # fresh: torch may keep these views as .grad
-            g, off = {}, 0
-            for name, sh, k in zip(ctx.names, ctx.shapes, sizes):
-                g[name] = flat[off:off + k].view(sh)
-                off += k
+            flat, g = carve_grads(ctx.names, ctx.shapes, engine.dev)
             dx = None
             if ctx.needs_input_grad[0]:                 # d loss / d frame: the reference's autograd yields it (models/stofnet.py:45)
                 dx = torch.empty_like(saved.x)                    # [N, L], or [N, Cin, L] for in_channels > 1
