@@ -353,6 +353,52 @@ size_t stof_zonzini_workspace_bytes(const stof_zonzini_desc* desc, int64_t N, in
 int stof_zonzini_forward(const stof_zonzini_desc* desc, const float* x, int64_t N, int64_t L, const void* packed,
                          float* y, float* features, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same nets for training (csrc/zonzini_train.hip): one entry per stage, exact fp32, fixed summation orders, no float atomic
+ * and no library call; two runs give bitwise equal results.  Buffers of conv layer l (0-based; Lp_l its pooled length, cpad_l
+ * its channels rounded up to 4): act_l [N][Lp_l][cpad_l] fp32, pad channels 0; sel_l [N][Lp_l][cpad_l] bytes: 0 = the stored
+ * output is not > 0 (no gradient), 1 = conv output 2p won the pool, 2 = conv output 2p + 1 won (a tie goes to 2p, as in
+ * max_pool1d's backward).  Every entry takes the frame's N and L and derives each layer's lengths from them.  Argument checks
+ * come before any HIP call, as for stof_zonzini_forward: NULL pointers, N <= 0, an unknown variant or a layer outside
+ * 1 .. layers - 1 -> STOF_ERR_BAD_ARG, L below the minimum -> STOF_ERR_POOL_EMPTY, N L >= 2^31 -> STOF_ERR_UNSUPPORTED, a short
+ * workspace -> STOF_ERR_WORKSPACE.  All buffers are 16-byte aligned.
+ *
+ *   stof_zonzini_train_pack        stof_zonzini_pack_weights on the device: params = the same pointers in the same order, in
+ *                                  device memory; out = stof_zonzini_packed_bytes(desc) bytes of device memory, byte for byte
+ *                                  the host packer's blob (a training step packs again after every optimizer step)
+ *   stof_zonzini_train_forward     the inference chain, keeping acts[l] and sel[l] of every layer, f [N][C_last] (the global
+ *                                  mean) and h [N][1024] (fc1 after ReLU); y [N] is bitwise stof_zonzini_forward's
+ *   stof_zonzini_train_head_bwd    from dy [N]: dfc1w [1024][C], dfc1b, dfc2w [1024], dfc2b (sums over n = 0 .. N - 1 in order)
+ *                                  and df [N][cpad_last] (pad 0).  fc1w, fc2w: the parameters in torch layout.
+ *   stof_zonzini_train_conv_wgrad  layer >= 1 on v_mfma_f32_32x32x2_f32: dw (cout, cin, 10), db (cout) from in = act_(layer-1),
+ *                                  sel = sel_layer and dout = the gradient of act_layer [N][Lp][cpad] -- for the last layer df of
+ *                                  the head instead, whose readers divide by Lp on the fly.  Per-chunk partials in the workspace
+ *                                  (stof_zonzini_train_conv_wgrad_workspace_bytes, at most 64 MiB), added in a fixed order.
+ *   stof_zonzini_train_dgrad_image layer's weight (cout, cin, 10) -> the stof_zonzini_train_dgrad_image_floats floats of the
+ *                                  operand image of stof_zonzini_train_conv_dgrad (on the device; again when the weight changes)
+ *   stof_zonzini_train_conv_dgrad  din [N][Lp_(layer-1)][cpad_(layer-1)] = the gradient of act_(layer-1); rows that no kept conv
+ *                                  output reads are exactly 0.  The ReLU / pool of layer - 1 is applied by din's readers (sel).
+ *   stof_zonzini_train_in_wgrad    layer 0 (Cin = 1, vector pipe): dw (cout, 1, 10), db (cout) from x [N][L], dout and sel_0
+ *   stof_zonzini_train_in_dgrad    dx [N][L] from dout, sel_0 and w = conv_layers.0.weight; samples past the last kept window 0.0 */
+int stof_zonzini_train_pack(const stof_zonzini_desc* desc, const float* const* params, void* out, size_t out_bytes, void* stream);
+int stof_zonzini_train_forward(const stof_zonzini_desc* desc, const float* x, int64_t N, int64_t L, const void* packed,
+                               float* const* acts, uint8_t* const* sel, float* f, float* h, float* y, void* stream);
+int stof_zonzini_train_head_bwd(const stof_zonzini_desc* desc, const float* dy, const float* f, const float* h, const float* fc1w,
+                                const float* fc2w, float* dfc1w, float* dfc1b, float* dfc2w, float* dfc2b, float* df, int64_t N,
+                                void* stream);
+size_t stof_zonzini_train_conv_wgrad_workspace_bytes(const stof_zonzini_desc* desc, int32_t layer);
+int stof_zonzini_train_conv_wgrad(const stof_zonzini_desc* desc, int32_t layer, const float* in, const float* dout,
+                                  const uint8_t* sel, float* dw, float* db, int64_t N, int64_t L, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+size_t stof_zonzini_train_dgrad_image_floats(const stof_zonzini_desc* desc, int32_t layer);
+int stof_zonzini_train_dgrad_image(const stof_zonzini_desc* desc, int32_t layer, const float* w, float* out, void* stream);
+int stof_zonzini_train_conv_dgrad(const stof_zonzini_desc* desc, int32_t layer, const float* dout, const uint8_t* sel,
+                                  const float* image, float* din, int64_t N, int64_t L, void* stream);
+size_t stof_zonzini_train_in_wgrad_workspace_bytes(const stof_zonzini_desc* desc);
+int stof_zonzini_train_in_wgrad(const stof_zonzini_desc* desc, const float* x, const float* dout, const uint8_t* sel, float* dw,
+                                float* db, int64_t N, int64_t L, void* workspace, size_t workspace_bytes, void* stream);
+int stof_zonzini_train_in_dgrad(const stof_zonzini_desc* desc, const float* dout, const uint8_t* sel, const float* w, float* dx,
+                                int64_t N, int64_t L, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * SincNet baseline (models/sincnet.py: SincNet with the option dict of main.py:145-157: sinc conv 128 x 1023 taps,
  * Conv1d 128->128 k 11, 128->128 k 9, 128->1 k 7, each "same" padded + BatchNorm1d (eval) + LeakyReLU(0.2), the

@@ -10,7 +10,8 @@ load_state_dict (main.py:173-177), the eval loop's `model(frame)` -> `mask2coord
 summed validation loss, checkpoint `<run_name>_rf-scale<rf>_epoch_<e>.pth`, main.py:423-426) on the
 HIP training kernels, for model=stofnet, model=edsr and model=espcn (EDSR_1D, ESPCN_1D: torch loss and optimizer on the module's
 autograd boundary, exact fp32; `train_route=kernels` runs the backward pass on the gfx950 kernels, `train_route=aten` on stock ATen
-layers; every other model evaluates only); launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
+layers; model=zonzini trains the same way with `zonzini_loss`, the reference's main.py:233-241, its route switch being
+`train_route=kernels|aten` too; every other model evaluates only); launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
 one flat gradient all-reduce per step over RCCL).  `augment=True` puts the reference's training transforms in front of every
 training step (main.py:49,54,82: CropChannelData(crop_ratio) + AddNoise(snr_db) on chirp data, AddNoise alone otherwise) as
 one launch of the device kernel (stofnet_amd/augment.py); `shuffle=True` reorders the training rows every epoch
@@ -113,8 +114,7 @@ def main(argv=None):
     elif name == 'espcn':
         model = ESPCN_1D(upscale_factor=cfg.upsample_factor)                  # trains: train()
     elif name == 'zonzini':                                               # main.py:135-136: Small on chirp data, else Large
-        model = ZonziniNetSmall() if 'chirp' in str(cfg.data_dir).lower() else ZonziniNetLarge()
-        cfg.evaluate = True                                               # inference only on the gfx950 path
+        model = ZonziniNetSmall() if 'chirp' in str(cfg.data_dir).lower() else ZonziniNetLarge()       # trains: train()
     elif name == 'kuleshov':                                              # main.py:137-138
         model = Kuleshov(input_length=int(frames.shape[-1]), output_length=int(frames.shape[-1]) * int(cfg.upsample_factor))
         cfg.evaluate = True                                               # inference only on the gfx950 path
@@ -163,18 +163,34 @@ def main(argv=None):
     log = RunLog(cfg)
     if log.enabled and str(cfg.run_name) == 'local-run':
         cfg.run_name = log.name                                          # the reference names checkpoints after the wandb run
-    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name in ('stofnet', 'edsr', 'espcn')) else None
+    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name in ('stofnet', 'edsr', 'espcn', 'zonzini')) else None
     es_all, summary = evaluate(model, name, frames, gt, cfg, log)
     log.summary({'model_name': name, 'total_parameters': int(sum(p.numel() for p in model.parameters())),
                  'total_jaccard': summary.get('total_jaccard'), 'total_inference_time': summary['inference_time'],
                  'total_distance_mean': summary.get('total_distance_mean'), 'total_distance_std': summary.get('total_distance_std')})
     if history is not None:
         summary['train_history'] = history
-        if name in ('edsr', 'espcn'):
+        if name in ('edsr', 'espcn', 'zonzini'):
             summary['train_route'], summary['train_precision'] = model.train_route, 'fp32'
     if int(os.environ.get('RANK', '0')) == 0:
         print(json.dumps(summary))
     return es_all, summary
+
+
+def zonzini_loss(pred, gt_sample, r):
+    """The Zonzini branch of the reference's loss (main.py:233-241, validation :332-342): pred [N, 1] against the ground-truth
+    value of each row's first onset, gt_sample [N, K] (slots <= 0 or NaN are empty, main.py:217).
+
+    The onset picked is the slot with the smallest non-zero sample index `round(gt r) // r` (main.py:218,236-239; the first
+    such slot on a tie, slot 0 when the row has none, whose value is then 0).  The reference hands `MSELoss` pred [N, 1] and
+    the gathered targets t [N, 1, 1]; they broadcast to [N, N, 1] (torch warns), so its loss is the mean over ALL PAIRS,
+    sum over n, m of (pred_n - t_m)^2 / N^2, not the row-wise mean.  That value and its gradient are kept."""
+    gt = torch.nan_to_num(gt_sample.to(pred.device), nan=0.0)
+    gt = torch.where(gt <= 0, torch.zeros_like(gt), gt)                                          # main.py:217
+    idx = torch.round(gt * r).long() // int(r)                                                   # main.py:218,236
+    idx = torch.where(idx == 0, torch.full_like(idx, 10 ** 12), idx)                             # main.py:238
+    t = torch.gather(gt, -1, torch.argmin(idx, dim=-1, keepdim=True)).to(pred.dtype)             # main.py:239-240, [N, 1]
+    return ((pred.reshape(1, -1) - t.reshape(-1, 1)) ** 2).mean()                                # main.py:241
 
 
 def epoch_batches(n_rows, bs, epoch, rank, world, shuffle=False, seed=0):
@@ -195,7 +211,8 @@ def train(model, frames, gt, cfg, log=None):
     StofNet trains through `StofNetTrainer` or, with trainer=autograd, through the reference's own torch lines on the module's
     autograd boundary.  EDSR_1D (model=edsr) and ESPCN_1D (model=espcn) always take those torch lines, in exact fp32 whatever
     `train_precision` says: with train_route=kernels `loss.backward()` runs the gfx950 kernels (stofnet_amd/edsr_training.py,
-    stofnet_amd/espcn_training.py), with train_route=aten the same loop runs on stock ATen layers.
+    stofnet_amd/espcn_training.py), with train_route=aten the same loop runs on stock ATen layers.  The Zonzini nets
+    (model=zonzini) take the same lines and the same switch (stofnet_amd/zonzini_training.py) with `zonzini_loss` as their loss.
 
     With `augment=True` every training batch goes through stofnet_amd.augment.Augment first (generator: seed = cfg.seed,
     rank = RANK, one `call` per step) and the ground truth moves with the crop window before it becomes sample indices.
@@ -210,7 +227,8 @@ def train(model, frames, gt, cfg, log=None):
     rank = int(os.environ.get('RANK', '0'))
     if world > 1 and not dist.is_initialized():
         dist.init_process_group('nccl', device_id=torch.device(cfg.device))
-    routed = isinstance(model, (EDSR_1D, ESPCN_1D))                     # the baselines with a `train_route` switch
+    zonzini = isinstance(model, (ZonziniNetSmall, ZonziniNetLarge))
+    routed = zonzini or isinstance(model, (EDSR_1D, ESPCN_1D))          # the baselines with a `train_route` switch
     tr = None if routed else StofNetTrainer(model, lr=cfg.lr, weight_decay=cfg.weight_decay, lambda_value=cfg.lambda_value,
                                             mask_amplitude=cfg.mask_amplitude, kernel_size=cfg.kernel_size, sigma=cfg.sigma,
                                             precision=cfg.train_precision)
@@ -228,6 +246,8 @@ def train(model, frames, gt, cfg, log=None):
     best, bad, history = float('inf'), 0, []
 
     def gt_true_of(g):
+        if zonzini:                                                      # `zonzini_loss` takes the ground truth as it is
+            return torch.from_numpy(g).to(cfg.device) if isinstance(g, np.ndarray) else g
         if isinstance(g, np.ndarray):
             g = torch.from_numpy(np.nan_to_num(g, nan=0.0)).to(cfg.device)
         else:
@@ -256,6 +276,8 @@ def train(model, frames, gt, cfg, log=None):
                              device=cfg.device).unsqueeze(0).unsqueeze(0)
 
         def torch_loss(masks_pred, gt_true, sharded=True):
+            if zonzini:
+                return zonzini_loss(masks_pred, gt_true, r)                                      # main.py:233-241
             masks_true = coords2mask(gt_true, masks_pred)                                        # main.py:228
             blur = F.conv1d(masks_true, gauss, padding=int(cfg.kernel_size) // 2)                # main.py:229
             bmax = blur.max().reshape(1)

@@ -1,6 +1,7 @@
 """Drop-in for the reference's `models` package (models/__init__.py): `from models import StofNet, ..., GradPeak`
-(main.py:18) resolves unchanged.  StofNet, GradPeak and the Zonzini baselines (ZonziniNetSmall / ZonziniNetLarge,
-inference only) run on the gfx950 kernels (stofnet_amd); EDSR_1D(1, 64, B, r | 64) and ESPCN_1D(r <= 64) run inference
+(main.py:18) resolves unchanged.  StofNet, GradPeak and the Zonzini baselines (ZonziniNetSmall / ZonziniNetLarge:
+inference, and with the opt-in `train_route = 'kernels'` training, stofnet_amd/zonzini_training.py; the class default None
+still raises where a graph would be recorded, 'aten' runs the module's own layers) run on the gfx950 kernels (stofnet_amd); EDSR_1D(1, 64, B, r | 64) and ESPCN_1D(r <= 64) run inference
 on the gfx950 kernels of csrc/riders.hip and keep the stock ATen route with the SampleShuffle1D kernel for training and
 for other widths (stofnet_amd/baselines.py); SincNet runs on the gfx950 kernels for the option dict of
 main.py (inference only; SincNet() without options raises NotImplementedError); WaveUnet(n_layers = 1 .. 12,

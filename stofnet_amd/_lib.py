@@ -145,6 +145,22 @@ _SIGNATURES = {
     'stof_zonzini_workspace_bytes': (_c.c_size_t, [_c.POINTER(ZonziniDesc), _c.c_int64, _c.c_int64]),
     'stof_zonzini_forward': (_c.c_int, [_c.POINTER(ZonziniDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
                                         _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_zonzini_train_pack': (_c.c_int, [_c.POINTER(ZonziniDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_zonzini_train_forward': (_c.c_int, [_c.POINTER(ZonziniDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p,
+                                              _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_void_p,
+                                              _c.c_void_p, _c.c_void_p]),
+    'stof_zonzini_train_head_bwd': (_c.c_int, [_c.POINTER(ZonziniDesc)] + [_c.c_void_p] * 10 + [_c.c_int64, _c.c_void_p]),
+    'stof_zonzini_train_conv_wgrad_workspace_bytes': (_c.c_size_t, [_c.POINTER(ZonziniDesc), _c.c_int32]),
+    'stof_zonzini_train_conv_wgrad': (_c.c_int, [_c.POINTER(ZonziniDesc), _c.c_int32] + [_c.c_void_p] * 5 +
+                                      [_c.c_int64, _c.c_int64, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_zonzini_train_dgrad_image_floats': (_c.c_size_t, [_c.POINTER(ZonziniDesc), _c.c_int32]),
+    'stof_zonzini_train_dgrad_image': (_c.c_int, [_c.POINTER(ZonziniDesc), _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_zonzini_train_conv_dgrad': (_c.c_int, [_c.POINTER(ZonziniDesc), _c.c_int32] + [_c.c_void_p] * 4 +
+                                      [_c.c_int64, _c.c_int64, _c.c_void_p]),
+    'stof_zonzini_train_in_wgrad_workspace_bytes': (_c.c_size_t, [_c.POINTER(ZonziniDesc)]),
+    'stof_zonzini_train_in_wgrad': (_c.c_int, [_c.POINTER(ZonziniDesc)] + [_c.c_void_p] * 5 +
+                                    [_c.c_int64, _c.c_int64, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_zonzini_train_in_dgrad': (_c.c_int, [_c.POINTER(ZonziniDesc)] + [_c.c_void_p] * 4 + [_c.c_int64, _c.c_int64, _c.c_void_p]),
     'stof_sincnet_packed_bytes': (_c.c_size_t, [_c.POINTER(SincNetDesc)]),
     'stof_sincnet_pack_weights': (_c.c_int, [_c.POINTER(SincNetDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
     'stof_sincnet_filter_bank': (_c.c_int, [_c.POINTER(SincNetDesc), _c.c_void_p, _c.c_void_p, _c.c_void_p]),

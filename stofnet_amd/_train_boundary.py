@@ -2,7 +2,7 @@
 their kernels, and `carve_grads`, which StofNet's own boundary (`training.StofNetFunction`) uses too:
 
   carve_grads      one fresh flat gradient buffer per backward, carved into the parameters' shapes
-  SavedStepEngine  the base of an engine with `_forward_saved(p, frame) -> (y [N, L r], saved)` and
+  SavedStepEngine  the base of an engine with `_forward_saved(p, frame) -> (y [N, out columns], saved)` and
                    `_backward_saved(saved, dy, g, dx)`: the frame flattening, the check that no parameter changed between
                    the two, and the cache of kernel-layout weight images
   EndsFunction     the autograd boundary over such an engine"""
@@ -32,6 +32,10 @@ class SavedStepEngine(LayerKernels):
         super().__init__(dev, _lib.PREC_FP32)
         self.r = int(r)
         self._images = {}           # key -> ((data_ptr, _version) of the weight, its kernel-layout image)
+
+    def out_shape(self, n, L):
+        """shape of `model(frame)` for a frame [n, 1, L]: the upsampled row of the SampleShuffle1D nets"""
+        return (n, 1, L * self.r)
 
     def _flat_frame(self, frame):
         """frame [N, 1, L] -> x [N, L] float32, detached"""
@@ -67,10 +71,10 @@ class EndsFunction(torch.autograd.Function):
         ctx.engine, ctx.names, ctx.shapes, ctx.dims = engine, names, [tuple(v.shape) for v in params], (n, L)
         if n == 0 or L == 0:
             ctx.saved = ()
-            return torch.empty((n, 1, L * engine.r), dtype=torch.float32, device=engine.dev)
+            return torch.empty(engine.out_shape(n, L), dtype=torch.float32, device=engine.dev)
         with torch.cuda.device(engine.dev):
             y, ctx.saved = engine._forward_saved({k: v.detach() for k, v in zip(names, params)}, frame)
-        return y.view(n, 1, L * engine.r)
+        return y.view(engine.out_shape(n, L))
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -82,6 +86,6 @@ class EndsFunction(torch.autograd.Function):
             _, g = carve_grads(ctx.names, ctx.shapes, engine.dev)
             dx = torch.empty((n, L), dtype=torch.float32, device=engine.dev) if ctx.needs_input_grad[0] else None
             if n and L:
-                engine._backward_saved(saved, grad_out.detach().reshape(n, L * engine.r).contiguous().float(), g, dx)
+                engine._backward_saved(saved, grad_out.detach().reshape(n, -1).contiguous().float(), g, dx)
         ctx.saved = None
         return (None if dx is None else dx.view(n, 1, L), None, None) + tuple(g[name] for name in ctx.names)

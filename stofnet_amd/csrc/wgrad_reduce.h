@@ -47,6 +47,19 @@ struct TapsThenBiasPerInput {
     }
 };
 
+// a strided convolution's partial in the k order its kernels read: elements co * K + tap * cpad_in + ci -> dw (cout, cin, taps),
+// then cout bias slots -> db; the slots of the pad channels ci >= cin are never stored
+struct ConvTapsThenBias {
+    float *dw, *db;
+    int cout, cin, cpad_in, K, taps;
+    __device__ bool used(int i) const { return i >= cout * K || (i % K) % cpad_in < cin; }
+    __device__ void store(int i, float v) const {
+        if (i >= cout * K) { db[i - cout * K] = v; return; }
+        const int co = i / K, k = i - co * K, tap = k / cpad_in, ci = k - tap * cpad_in;
+        dw[((size_t)co * cin + ci) * taps + tap] = v;
+    }
+};
+
 template <class Map>
 __global__ __launch_bounds__(1024) void partial_reduce_kernel(const float* __restrict__ copies, int ncopies, int stride, int E, Map map,
                                                               float out_scale) {

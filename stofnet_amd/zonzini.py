@@ -1,9 +1,9 @@
 """The Zonzini baselines of the reference (models/zonzini.py: ZonziniNetSmall, ZonziniNetLarge) on the gfx950 kernels
-of csrc/zonzini.hip, inference only.
+of csrc/zonzini.hip (inference) and, opt-in through `train_route`, csrc/zonzini_train.hip (training, zonzini_training.py).
 
 Constructor (no arguments), module and parameter names (`conv_layers.{i}.*`, `fc1.*`, `fc2.*`), shapes and default
 initialisation are the reference's, so its checkpoints load with strict=True.  The layers are parameter holders: the
-forward never calls their ATen kernels.  It packs the parameters once per change (their `_version` counters and
+inference forward never calls their ATen kernels (only `train_route = 'aten'` does).  It packs the parameters once per change (their `_version` counters and
 storage), splits the batch into chunks whose workspace stays under `max_workspace_bytes`, and launches the HIP
 forward on the current stream.  Rows are independent and bitwise independent of the batch they sit in, so the
 chunking does not show in the result."""
@@ -23,6 +23,11 @@ class _ZonziniNet(_PackedKernels, nn.Module):
     CHANNELS = ()
     MIN_LEN = 0
     max_workspace_bytes = 512 << 20
+    # None | 'kernels' | 'aten': what `forward` does where an autograd graph would be recorded (grad enabled and the module
+    # in train mode or x asking for a gradient).  None raises NotImplementedError; 'kernels' goes through the autograd
+    # boundary of zonzini_training.py (gfx950 kernels, exact fp32); 'aten' runs the module's own Conv1d / MaxPool1d / Linear
+    # layers as the reference's forward does.  Every other call stays on the inference kernels.
+    train_route = None
 
     def __init__(self):
         super().__init__()
@@ -56,7 +61,7 @@ class _ZonziniNet(_PackedKernels, nn.Module):
             raise TypeError(f'{type(self).__name__}: x must be float32 (got {x.dtype}); the gfx950 kernels are fp32 only')
         if x.dim() != 3 or x.shape[1] != 1:
             raise RuntimeError(f'{type(self).__name__}: expected x of shape [N, 1, L], got {list(x.shape)}')
-        if torch.is_grad_enabled() and (self.training or x.requires_grad):
+        if self._records_graph(x):
             raise NotImplementedError(f'{type(self).__name__}: Zonzini training is not implemented on the gfx950 path '
                                       '(inference only: call model.eval() or run under torch.no_grad())')
         L = int(x.shape[-1])
@@ -68,7 +73,42 @@ class _ZonziniNet(_PackedKernels, nn.Module):
         """(y [N, 1], the global average pool's output [N, C_last]), both float32."""
         return self._run(x, True)
 
+    def _records_graph(self, x):
+        """Where the inference kernels cannot serve: an autograd graph would be recorded."""
+        return torch.is_grad_enabled() and (self.training or x.requires_grad)
+
+    def forward_aten(self, x):
+        """The reference's forward on the module's own ATen layers (models/zonzini.py:25-37)."""
+        for conv in self.conv_layers:
+            x = self.maxpool(self.relu(conv(x)))
+        x = self.global_avgpool(x)
+        x = x.view(x.size(0), -1)
+        return self.fc2(self.relu(self.fc1(x)))
+
+    def forward_train_kernels(self, x):
+        """y [N, 1] float32 on the gfx950 training kernels (zonzini_training.py), with an autograd graph: its backward fills
+        the gradient of every parameter (and of x, if it asks for one) in exact fp32.  Not chunked by `max_workspace_bytes`:
+        the backward needs every activation of the whole batch."""
+        from .zonzini_training import ZonziniFunction, ZonziniTrainEngine
+        with torch.no_grad():                                # the checks of an inference call, minus the graph condition
+            self._check_input(x)
+        names, params = zip(*self.named_parameters())
+        for p in params:
+            if p.dtype != torch.float32:
+                raise TypeError(f'{type(self).__name__}: parameters must be float32 (got {p.dtype}); the gfx950 kernels are '
+                                'fp32 only')
+            _lib.require_device(p, 'parameter')
+        engines = self.__dict__.setdefault('_train_engines', {})
+        key = str(x.device)
+        if key not in engines:
+            engines[key] = ZonziniTrainEngine(x.device, self.VARIANT)
+        return ZonziniFunction.apply(x, engines[key], names, *params)
+
     def forward(self, x):
+        if self.train_route not in (None, 'kernels', 'aten'):
+            raise ValueError(f"{type(self).__name__}.train_route must be None, 'kernels' or 'aten' (got {self.train_route!r})")
+        if self.train_route is not None and self._records_graph(x):
+            return self.forward_train_kernels(x) if self.train_route == 'kernels' else self.forward_aten(x)
         return self._run(x, False)[0]
 
     def _run(self, x, want_features):
