@@ -433,6 +433,62 @@ size_t stof_sincnet_workspace_bytes(const stof_sincnet_desc* desc, int64_t N, in
  * STOF_ERR_BAD_ARG, workspace too small -> STOF_ERR_WORKSPACE, N (L + 8) >= 2^31 -> STOF_ERR_UNSUPPORTED.           */
 int stof_sincnet_forward(const stof_sincnet_desc* desc, const float* x, int64_t N, int64_t L, const void* packed,
                          float* y, void* workspace, size_t workspace_bytes, void* stream);
+/* The chain rule of the filter synthesis on the host, in double: bank_grad[128][1023] = d loss / d bank ->
+ * dlow_hz[128], dband_hz[128] = d loss / d low_hz_, band_hz_ (through the window, the divisions, the mirrored right half,
+ * the constant centre tap, clamp: gradient 1 inside the closed interval, else 0, and abs: the sign, 0 at 0).        */
+int stof_sincnet_band_grad(const stof_sincnet_desc* desc, const float* low_hz, const float* band_hz, const float* bank_grad,
+                           double* dlow_hz, double* dband_hz);
+
+/* SincNet training in exact fp32 (csrc/sincnet_train.hip; the host side is stofnet_amd/sincnet_training.py), one entry per
+ * stage, all on `stream` without a host sync, an allocation or a float atomic.  128-channel tensors are in the GAP layout of
+ * the inference workspace, (N (L + 8) + 8) x 128 floats (stof_sincnet_train_buffer_floats, 0 for bad dimensions), row
+ * 8 + n (L + 8) + t, zero gap rows; every entry that writes such a tensor zeroes its gap rows.  The one-channel tensors of
+ * layer 3 are flat [N L].  `channels` is 128 or 1.  BatchNorm runs in train mode: batch statistics over the N L >= 2 rows,
+ * sums in double.  The module's running statistics are read, never written: the new ones go to new_mean / new_var.     */
+size_t stof_sincnet_train_buffer_floats(int64_t N, int64_t L);
+/* out[0..5]: float offsets of frag0, bank_t [1024][128], frag1, frag2, w3 [7][128] in the training blob, and its size */
+int stof_sincnet_train_blob_layout(int64_t* out);
+/* params (device): low_hz_, band_hz_, conv.1.weight, conv.2.weight, conv.3.weight -> the blob of the forward kernels;
+ * the bank is synthesised in double on the device.                                                                   */
+int stof_sincnet_train_pack(const stof_sincnet_desc* desc, const float* const* params, void* out, size_t out_bytes, void* stream);
+/* stof_sincnet_pack_weights on the device: the same 24 arrays in device memory -> the inference blob, the host packer's
+ * bytes up to the last bit of the device's sin / cos (no trip through the host after an optimizer step).                 */
+int stof_sincnet_device_pack(const stof_sincnet_desc* desc, const float* const* params, void* out, size_t out_bytes, void* stream);
+/* the flipped, transposed fragment image of conv.`layer`.weight (layer 1 or 2; 128 x taps x 128 floats)               */
+int stof_sincnet_train_dgrad_image(int32_t layer, const float* w, float* out, void* stream);
+/* z_l = conv_l(in) + bias without BatchNorm.  layer 0: in = x [N][L] (bias ignored); 1, 2: in = a_{l-1}; 3: in = a_2 and
+ * out = z_3 [N L]                                                                                                      */
+int stof_sincnet_train_conv(int32_t layer, const float* in, int64_t N, int64_t L, const void* blob_dev, const float* bias,
+                            float* out, void* stream);
+int stof_sincnet_train_conv_dgrad(int32_t layer, const float* dz, int64_t N, int64_t L, const float* image, float* da, void* stream);
+size_t stof_sincnet_train_stats_workspace_bytes(void);
+/* stat [4][channels] doubles: mean, rstd, s = gamma rstd and t = beta - mean s                                       */
+int stof_sincnet_train_stats(const stof_sincnet_desc* desc, const float* z, int64_t N, int64_t L, int32_t channels,
+                             const float* gamma, const float* beta, const float* run_mean, const float* run_var,
+                             double momentum, double* stat, float* new_mean, float* new_var, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* a = leaky(z s + t) (channels = 128) or y = z s + t (channels = 1), the affine in double and rounded once            */
+int stof_sincnet_train_apply(const float* z, int64_t N, int64_t L, int32_t channels, const double* stat, float* out, void* stream);
+/* da (channels = 1: dy), a (the LeakyReLU decision is a > 0; NULL for channels = 1), z, stat -> dgamma, dbeta, dz       */
+int stof_sincnet_train_bn_bwd(const float* da, const float* a, const float* z, const double* stat, const float* gamma,
+                              int64_t N, int64_t L, int32_t channels, float* dgamma, float* dbeta, float* dz,
+                              void* workspace, size_t workspace_bytes, void* stream);
+size_t stof_sincnet_train_conv_wgrad_workspace_bytes(int32_t layer);
+int stof_sincnet_train_conv_wgrad(int32_t layer, const float* a_prev, const float* dz, int64_t N, int64_t L, float* dw,
+                                  float* db, void* workspace, size_t workspace_bytes, void* stream);
+size_t stof_sincnet_train_out_wgrad_workspace_bytes(void);
+int stof_sincnet_train_out_wgrad(const float* a2, const float* dz3, int64_t N, int64_t L, float* dw, float* db, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int stof_sincnet_train_out_dgrad(const float* dz3, const float* w, int64_t N, int64_t L, float* da2, void* stream);
+size_t stof_sincnet_train_bank_grad_workspace_bytes(void);
+/* G [128][1023] = d loss / d bank from x [N][L] and dz_0                                                               */
+int stof_sincnet_train_bank_grad(const float* x, const float* dz0, int64_t N, int64_t L, float* G, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+/* stof_sincnet_band_grad on the device, rounded to fp32                                                                */
+int stof_sincnet_train_band_grad(const stof_sincnet_desc* desc, const float* low_hz, const float* band_hz, const float* G,
+                                 float* dlow_hz, float* dband_hz, void* stream);
+/* dx [N][L] from dz_0 and the training blob (vector pipe; only when the frame asks for its gradient)                   */
+int stof_sincnet_train_in_dgrad(const float* dz0, const void* blob_dev, int64_t N, int64_t L, float* dx, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * EDSR_1D and ESPCN_1D (models/edsr_1d.py, models/espcn_1d.py), the baselines riding on SampleShuffle1D, inference

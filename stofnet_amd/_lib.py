@@ -167,6 +167,33 @@ _SIGNATURES = {
     'stof_sincnet_workspace_bytes': (_c.c_size_t, [_c.POINTER(SincNetDesc), _c.c_int64, _c.c_int64]),
     'stof_sincnet_forward': (_c.c_int, [_c.POINTER(SincNetDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
                                         _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_sincnet_band_grad': (_c.c_int, [_c.POINTER(SincNetDesc)] + [_c.c_void_p] * 5),
+    'stof_sincnet_train_buffer_floats': (_c.c_size_t, [_c.c_int64, _c.c_int64]),
+    'stof_sincnet_train_blob_layout': (_c.c_int, [_c.POINTER(_c.c_int64)]),
+    'stof_sincnet_train_pack': (_c.c_int, [_c.POINTER(SincNetDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_sincnet_device_pack': (_c.c_int, [_c.POINTER(SincNetDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_sincnet_train_dgrad_image': (_c.c_int, [_c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_sincnet_train_conv': (_c.c_int, [_c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                           _c.c_void_p]),
+    'stof_sincnet_train_conv_dgrad': (_c.c_int, [_c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_sincnet_train_stats_workspace_bytes': (_c.c_size_t, []),
+    'stof_sincnet_train_stats': (_c.c_int, [_c.POINTER(SincNetDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32] + [_c.c_void_p] * 4 +
+                                 [_c.c_double] + [_c.c_void_p] * 4 + [_c.c_size_t, _c.c_void_p]),
+    'stof_sincnet_train_apply': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_sincnet_train_bn_bwd': (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int64, _c.c_int64, _c.c_int32] + [_c.c_void_p] * 4 +
+                                  [_c.c_size_t, _c.c_void_p]),
+    'stof_sincnet_train_conv_wgrad_workspace_bytes': (_c.c_size_t, [_c.c_int32]),
+    'stof_sincnet_train_conv_wgrad': (_c.c_int, [_c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                                 _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_sincnet_train_out_wgrad_workspace_bytes': (_c.c_size_t, []),
+    'stof_sincnet_train_out_wgrad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                _c.c_size_t, _c.c_void_p]),
+    'stof_sincnet_train_out_dgrad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p]),
+    'stof_sincnet_train_bank_grad_workspace_bytes': (_c.c_size_t, []),
+    'stof_sincnet_train_bank_grad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                                _c.c_void_p]),
+    'stof_sincnet_train_band_grad': (_c.c_int, [_c.POINTER(SincNetDesc)] + [_c.c_void_p] * 6),
+    'stof_sincnet_train_in_dgrad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p]),
     'stof_edsr_packed_bytes': (_c.c_size_t, [_c.POINTER(EdsrDesc)]),
     'stof_edsr_pack_weights': (_c.c_int, [_c.POINTER(EdsrDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
     'stof_edsr_workspace_bytes': (_c.c_size_t, [_c.POINTER(EdsrDesc), _c.c_int64, _c.c_int64]),

@@ -60,6 +60,15 @@ struct ConvTapsThenBias {
     }
 };
 
+// the gradient of a bank of `taps` taps per filter computed `stride` wide: elements filter * stride + tap -> G (filter, taps);
+// the slots tap >= taps are never stored
+struct BankTaps {
+    float* G;
+    int taps, stride;
+    __device__ bool used(int i) const { return i % stride < taps; }
+    __device__ void store(int i, float v) const { G[(size_t)(i / stride) * taps + i % stride] = v; }
+};
+
 template <class Map>
 __global__ __launch_bounds__(1024) void partial_reduce_kernel(const float* __restrict__ copies, int ncopies, int stride, int E, Map map,
                                                               float out_scale) {

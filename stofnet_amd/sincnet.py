@@ -1,5 +1,6 @@
 """The SincNet baseline of the reference (models/sincnet.py: SincNet with the option dict of main.py:145-157) on the
-gfx950 kernels of csrc/sincnet.hip, inference only, exact fp32.
+gfx950 kernels of csrc/sincnet.hip (inference, exact fp32) and, opt-in through `train_route`, csrc/sincnet_train.hip
+(training with train-mode BatchNorm, sincnet_training.py).
 
 The module tree (`conv`, `bn`, `ln`, `act`, `drop`), parameter names, shapes and default initialisation are the
 reference's, so its checkpoints load with strict=True.  The layers are parameter holders: the forward never calls their
@@ -18,6 +19,7 @@ import math
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from ._kernel_route import _PackedKernels, _pack
@@ -127,6 +129,12 @@ class SincNet(_PackedKernels, nn.Module):
     LeakyReLU(0.2) (the last one linear).  x [N, L] or [N, 1, L] float32 -> y [N, 1, L]."""
     max_workspace_bytes = 512 << 20
     _PACKED_ARRAYS = 'parameters and BatchNorm statistics'
+    # None | 'kernels' | 'aten'.  None: every call behaves as an inference-only module (train mode and recorded graphs raise).
+    # Otherwise a train-mode call takes the training route whether or not a graph is recorded (train-mode BatchNorm uses batch
+    # statistics and updates the running ones under no_grad too): 'kernels' goes through the autograd boundary of
+    # sincnet_training.py (gfx950 kernels, exact fp32), 'aten' runs `forward_aten`.  Eval-mode calls that record no graph stay
+    # on the inference kernels; one that would record a graph runs `forward_aten` under 'aten' and raises under 'kernels'.
+    train_route = None
 
     def __init__(self, options=None):
         super().__init__()
@@ -183,22 +191,123 @@ class SincNet(_PackedKernels, nn.Module):
         fs, bn_eps = self._pack_key()
         return pack_weights(fs, host, bn_eps)
 
-    def _check_input(self, x):
-        if self.training:
-            raise NotImplementedError('SincNet: training is not implemented on the gfx950 path (in train mode the '
-                                      "reference's BatchNorm uses batch statistics, also under no_grad; call model.eval())")
+    def packed_weights(self, device):
+        """The inference blob.  With a training route set and every array on `device` it is packed there
+        (`device_pack_weights`: no device-to-host copy when a validation pass follows an optimizer step), else on the host."""
+        params = self._kernel_params()
+        if self.train_route is None or any(p.device != torch.device(device) or p.dtype != torch.float32 for p in params):
+            return super().packed_weights(device)
+        key = ('device', str(device), *self._pack_key()) + tuple((p.data_ptr(), p._version) for p in params)
+        if self._packed is None or self._packed_key != key:
+            self._packed = device_pack_weights(*self._pack_key(), [p.detach() for p in params])
+            self._packed_key = key
+        return self._packed
+
+    def _check_frame(self, x):
         _lib.require_device(x, 'x')
         if x.dtype != torch.float32:
             raise TypeError(f'SincNet: x must be float32 (got {x.dtype}); the gfx950 kernels are fp32 only')
         if not (x.dim() == 2 or (x.dim() == 3 and x.shape[1] == 1)):
             raise RuntimeError(f'SincNet: expected x of shape [N, L] or [N, 1, L], got {list(x.shape)}')
+
+    def _check_input(self, x):
+        if self.training:
+            raise NotImplementedError('SincNet: training is not implemented on the gfx950 path (in train mode the '
+                                      "reference's BatchNorm uses batch statistics, also under no_grad; call model.eval())")
+        self._check_frame(x)
         if torch.is_grad_enabled() and x.requires_grad:
             raise NotImplementedError('SincNet: backward is not implemented on the gfx950 path (inference only: run '
                                       'under torch.no_grad() or detach the input)')
         if int(x.shape[-1]) < 1:
             raise RuntimeError('SincNet: rows must hold at least one sample')
 
+    def _check_train_options(self):
+        if self.training and any(float(d) != 0.0 for d in self.cnn_drop):
+            raise NotImplementedError(f'SincNet: option cnn_drop={self.cnn_drop!r} is not supported on the training routes (live '
+                                      'dropout is not implemented; main.py uses 0.0)')
+
+    def sinc_filters(self):
+        """SincConv_fast's filter synthesis (models/sincnet.py:147-184) restated in torch on `low_hz_` / `band_hz_`, in their
+        dtype and on their device, with an autograd graph -> [128, 1, 1023]."""
+        sinc = self.conv[0]
+        low_p, band_p = sinc.low_hz_, sinc.band_hz_
+        dt, dev = low_p.dtype, low_p.device
+        k, fs = SINC_TAPS, sinc.sample_rate
+        n_lin = torch.linspace(0, (k / 2) - 1, steps=int(k / 2), dtype=dt, device=dev)
+        window = 0.54 - 0.46 * torch.cos(2 * math.pi * n_lin / k)
+        n = 2 * math.pi * torch.arange(-(k - 1) / 2.0, 0, dtype=dt, device=dev).view(1, -1) / fs
+        low = sinc.min_low_hz + torch.abs(low_p)
+        high = torch.clamp(low + sinc.min_band_hz + torch.abs(band_p), sinc.min_low_hz, fs / 2)
+        band = (high - low)[:, 0]
+        left = ((torch.sin(torch.matmul(high, n)) - torch.sin(torch.matmul(low, n))) / (n / 2)) * window
+        bank = torch.cat([left, 2 * band.view(-1, 1), torch.flip(left, dims=[1])], dim=1) / (2 * band[:, None])
+        return bank.view(N_FILT, 1, k)
+
+    def forward_aten(self, x):
+        """The reference's forward (models/sincnet.py:460-497) restated in torch on the module's own parameters: the sinc
+        filter synthesis, "same" zero padding, F.conv1d, then the module's `bn[i]`, `act[i]` and `drop[i]`.  Runs in the
+        parameters' dtype on their device (also the CPU, also float64), in train or eval mode."""
+        self._check_train_options()
+        p0 = self.conv[0].low_hz_
+        x = x.to(device=p0.device, dtype=p0.dtype)
+        n = int(x.shape[0])
+        x = x.reshape(n, 1, int(x.shape[-1]))
+        for i in range(4):
+            k = self.cnn_len_filt[i]
+            x = F.pad(x, ((k - 1) // 2, k - 1 - (k - 1) // 2))
+            z = F.conv1d(x, self.sinc_filters()) if i == 0 else F.conv1d(x, self.conv[i].weight, self.conv[i].bias)
+            x = self.drop[i](self.act[i](self.bn[i](z)))
+        return x.view(n, 1, -1)
+
+    def forward_train_kernels(self, x):
+        """y [N, 1, L] float32 of a train-mode call on the gfx950 training kernels (sincnet_training.py), with an autograd
+        graph when one is recorded: its backward fills the gradient of all 16 parameters (and of x, if it asks for one) in
+        exact fp32.  BatchNorm uses batch statistics and the running statistics are updated, also under no_grad.  Not chunked
+        by `max_workspace_bytes`: the batch statistics and the backward need every activation of the whole batch."""
+        from .sincnet_training import SincNetFunction, SincNetTrainEngine
+        if not self.training:
+            raise NotImplementedError("SincNet: train_route='kernels' serves train mode only; an eval-mode backward (running "
+                                      "statistics) is not implemented on the kernels (use train_route='aten' or torch.no_grad())")
+        self._check_train_options()
+        if isinstance(x, torch.Tensor) and x.dim() in (2, 3) and x.numel() == 1:                # torch's BatchNorm check, word for word
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size {torch.Size([1, N_FILT, 1])}')
+        self._check_frame(x)
+        N, L = int(x.shape[0]), int(x.shape[-1])
+        names, params = zip(*self.named_parameters())
+        for p in params:
+            if p.dtype != torch.float32:
+                raise TypeError(f'SincNet: parameters must be float32 (got {p.dtype}); the gfx950 kernels are fp32 only')
+            _lib.require_device(p, 'parameter')
+        desc = self._desc()
+        engines = self.__dict__.setdefault('_train_engines', {})
+        key = (str(x.device), desc.fs, desc.bn_eps)
+        if key not in engines:
+            engines[key] = SincNetTrainEngine(x.device, desc.fs, desc.bn_eps)
+        engine = engines[key]
+        engine.momentum = float(self.bn[0].momentum)
+        engine.running = [(bn.running_mean, bn.running_var) for bn in self.bn]
+        y = SincNetFunction.apply(x.reshape(N, 1, L), engine, names, *params)
+        if N and L:
+            with torch.no_grad():                # on the host side: `copy_` bumps the buffers' versions (the eval-mode blob's key)
+                for bn, (mean, var) in zip(self.bn, engine.new_running):
+                    bn.running_mean.copy_(mean)
+                    bn.running_var.copy_(var)
+                    bn.num_batches_tracked.add_(1)
+        return y
+
     def forward(self, x):
+        route = self.train_route
+        if route not in (None, 'kernels', 'aten'):
+            raise ValueError(f"SincNet.train_route must be None, 'kernels' or 'aten' (got {route!r})")
+        if route is not None:
+            if self.training:
+                return self.forward_train_kernels(x) if route == 'kernels' else self.forward_aten(x)
+            if torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad:
+                if route == 'aten':
+                    return self.forward_aten(x)
+                raise NotImplementedError("SincNet: an eval-mode call that records a graph is not implemented on train_route="
+                                          "'kernels' (the kernels' backward is the train-mode one, with batch statistics; use "
+                                          "train_route='aten', model.train() or torch.no_grad())")
         self._check_input(x)
         N, L = int(x.shape[0]), int(x.shape[-1])
         y = torch.empty((N, 1, L), dtype=torch.float32, device=x.device)
@@ -248,3 +357,23 @@ def pack_weights(fs, params, bn_eps=1e-5):
     if len(arrs) != 24:
         raise ValueError(f'SincNet packing needs 24 arrays, got {len(arrs)}')
     return _pack(lib.stof_sincnet_packed_bytes, lib.stof_sincnet_pack_weights, desc, arrs, 'stof_sincnet_pack_weights')
+
+
+def device_pack_weights(fs, bn_eps, params):
+    """`pack_weights` on the device (stof_sincnet_device_pack): the same 24 float32 arrays as tensors on one ROCm device -> the
+    blob there, a uint8 tensor.  No device-to-host copy; bitwise the host packer's blob on the tested parameter sets."""
+    lib = _lib.lib()
+    desc = _lib.SincNetDesc(float(fs), float(bn_eps), 0, 0)
+    nbytes = int(lib.stof_sincnet_packed_bytes(ctypes.byref(desc)))
+    if not nbytes:
+        raise ValueError(f'bad SincNet description (fs={fs!r}, bn_eps={bn_eps!r})')
+    if len(params) != 24:
+        raise ValueError(f'SincNet packing needs 24 arrays, got {len(params)}')
+    params = [_lib.require_device(p, 'parameter').contiguous() for p in params]
+    dev = params[0].device
+    blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ptrs = (ctypes.c_void_p * 24)(*[p.data_ptr() for p in params])
+    with torch.cuda.device(dev):
+        _lib.check(lib.stof_sincnet_device_pack(ctypes.byref(desc), ptrs, _lib.ptr(blob), nbytes, _lib.stream_ptr(dev)),
+                   'stof_sincnet_device_pack')
+    return blob
