@@ -550,6 +550,66 @@ int stof_waveunet_forward(const stof_waveunet_desc* desc, const float* x, int64_
                           float* bottleneck, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Wave-U-Net training (csrc/waveunet_train.hip): one entry per stage of a step, each on one convolution or one
+ * Conv + BatchNorm + LeakyReLU(0.1) block, exact fp32, no float atomic: two runs are bitwise equal.  Activations and
+ * gradients are dense channel-last fp32 [N, L, C] device arrays, C a multiple of 16 up to 384; taps is 15 or 5;
+ * `mode` names the virtual input of a convolution of output length Lout: 0 = every second position of src
+ * [N, 2 Lout, cin] (taps 15), 1 = the x2 align-corners interpolation of low [N, Lout / 2, cu] concatenated with src
+ * [N, Lout, cin - cu] (taps 5), 2 = src [N, Lout, cin].  Every entry launches on `stream` and returns a stof_status;
+ * the size functions return 0 for arguments they do not serve.  The chunk rules are documented in the .hip file.
+ * ------------------------------------------------------------------------- */
+/* out[10]: rows per partial / partials at the most of the statistics (0, 1), the head's weight gradient (2, 3),
+ * encoder 0's weight gradient (4, 5) and the convolutions' weight gradient (6, 7); the positions per tile (8); the
+ * largest low length M the interpolation transpose serves (9).                                                       */
+int stof_waveunet_train_constants(int64_t* out);
+/* Host only, no device: for M low positions the fp32 coordinates i0, i1, l0, l1 [2 M] of every high position as the
+ * kernels compute them, and the window lo, hi [M] (inclusive) of high positions that the transpose visits per low one. */
+int stof_waveunet_interp_table(int64_t M, int32_t* i0, int32_t* i1, float* l0, float* l1, int32_t* lo, int32_t* hi);
+/* The fragment image of weight w [cout][cin][taps] for stof_waveunet_train_conv: flip = 0 the forward's, flip = 1 the
+ * data gradient's (cin and cout swapped, taps reversed).                                                             */
+size_t stof_waveunet_train_frag_floats(int32_t cin, int32_t cout, int32_t taps, int32_t flip);
+int stof_waveunet_train_pack_frag(const float* w, int32_t cin, int32_t cout, int32_t taps, int32_t flip, float* frag, void* stream);
+/* encoder 0: weight [16][1][15], bias [16] -> image [256] */
+int stof_waveunet_train_pack_in(const float* w, const float* b, float* image, void* stream);
+/* encoder 0: z [N, L, 16] = conv(x [N, L]) + bias */
+int stof_waveunet_train_in_conv(const float* x, int64_t N, int64_t L, const float* image, float* z, void* stream);
+/* out [N, Lout, cout] = conv(virtual input) (+ bias, if not NULL); frag: an image whose input width is cin */
+int stof_waveunet_train_conv(const float* src, const float* low, int64_t N, int64_t Lout, int32_t cin, int32_t cu, int32_t cout,
+                             int32_t taps, int32_t mode, const float* frag, const float* bias, float* out, void* stream);
+size_t stof_waveunet_train_stats_workspace_bytes(void);
+/* z [rows, ch] -> stat [4][ch] double (mean, rstd, s, t) and the blended running statistics (not in place) */
+int stof_waveunet_train_stats(const float* z, int64_t rows, int32_t ch, const float* gamma, const float* beta, const float* run_mean,
+                              const float* run_var, double eps, double momentum, double* stat, float* new_mean, float* new_var,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* a = leaky_0.1(z s + t) */
+int stof_waveunet_train_apply(const float* z, int64_t rows, int32_t ch, const double* stat, float* a, void* stream);
+/* y [N, L] = tanh(w[0:16] . o [N, L, 16] + w[16] x + b) */
+int stof_waveunet_train_head(const float* o, const float* x, int64_t N, int64_t L, const float* w, const float* b, float* y, void* stream);
+size_t stof_waveunet_train_head_bwd_workspace_bytes(void);
+/* dout [N, L, 16], dw [17], db [1]; dxh [N, L] (NULL = not wanted) = w[16] dy (1 - y^2) */
+int stof_waveunet_train_head_bwd(const float* dy, const float* y, const float* o, const float* x, int64_t N, int64_t L, const float* w,
+                                 float* dout, float* dxh, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+/* da, a, z [rows, ch] -> dgamma, dbeta [ch], dz [rows, ch]; workspace as for the statistics */
+int stof_waveunet_train_bn_bwd(const float* da, const float* a, const float* z, const double* stat, int64_t rows, int32_t ch,
+                               float* dgamma, float* dbeta, float* dz, void* workspace, size_t workspace_bytes, void* stream);
+size_t stof_waveunet_train_wgrad_workspace_bytes(int64_t N, int64_t Lout, int32_t cin, int32_t cout, int32_t taps);
+/* dw [cout][cin][taps], db [cout] from dz [N, Lout, cout] and the forward's virtual input (cout <= 192) */
+int stof_waveunet_train_wgrad(const float* src, const float* low, const float* dz, int64_t N, int64_t Lout, int32_t cin, int32_t cu,
+                              int32_t cout, int32_t taps, int32_t mode, float* dw, float* db, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t stof_waveunet_train_in_wgrad_workspace_bytes(void);
+/* encoder 0: dw [16][1][15], db [16] from x [N, L] and dz [N, L, 16] */
+int stof_waveunet_train_in_wgrad(const float* x, const float* dz, int64_t N, int64_t L, float* dw, float* db, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+/* g [N, 2 M, cg] (its first cu channels) -> dlow [N, M, cu]: the transpose of the interpolation */
+int stof_waveunet_train_interp_t(const float* g, int64_t N, int64_t M, int32_t cg, int32_t cu, float* dlow, void* stream);
+/* out [N, L, cs] = gdec [N, L, cu + cs][.., cu:] + (at even positions) genc [N, L / 2, cs] */
+int stof_waveunet_train_skip_sum(const float* gdec, const float* genc, int64_t N, int64_t L, int32_t cu, int32_t cs, float* out,
+                                 void* stream);
+/* encoder 0: dx [N, L] = (dxh, if not NULL) + the data gradient of dz [N, L, 16] through w [16][1][15] */
+int stof_waveunet_train_in_dgrad(const float* dz, const float* w, const float* dxh, int64_t N, int64_t L, float* dx, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Kuleshov (models/kuleshov.py with num_layers = 4, `main.py model=kuleshov`), inference in exact fp32 with eval-mode
  * BatchNorm as a per-channel affine computed by the host packer in double.  Served: input_length >= 641 (the
  * shortest row for which every convolution has an output), output_length >= 1.  Conventions as for stof_edsr_*;

@@ -11,7 +11,8 @@ summed validation loss, checkpoint `<run_name>_rf-scale<rf>_epoch_<e>.pth`, main
 HIP training kernels, for model=stofnet, model=edsr and model=espcn (EDSR_1D, ESPCN_1D: torch loss and optimizer on the module's
 autograd boundary, exact fp32; `train_route=kernels` runs the backward pass on the gfx950 kernels, `train_route=aten` on stock ATen
 layers; model=zonzini trains the same way with `zonzini_loss`, the reference's main.py:233-241, its route switch being
-`train_route=kernels|aten` too; model=sincnet trains with the same lines and switch, train-mode BatchNorm included; every other model evaluates only); launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
+`train_route=kernels|aten` too; model=sincnet and model=unet
+train with the same lines and switch, train-mode BatchNorm included; every other model evaluates only); launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
 one flat gradient all-reduce per step over RCCL).  `augment=True` puts the reference's training transforms in front of every
 training step (main.py:49,54,82: CropChannelData(crop_ratio) + AddNoise(snr_db) on chirp data, AddNoise alone otherwise) as
 one launch of the device kernel (stofnet_amd/augment.py); `shuffle=True` reorders the training rows every epoch
@@ -137,8 +138,7 @@ def main(argv=None):
         if int(frames.shape[-1]) % (1 << n_layers):
             raise ValueError(f'model=unet with n_layers={n_layers} needs a frame length that is a multiple of '
                              f'{1 << n_layers} (got {int(frames.shape[-1])} samples)')
-        model = WaveUnet(n_layers=n_layers, channels_interval=16)
-        cfg.evaluate = True                                               # inference only on the gfx950 path
+        model = WaveUnet(n_layers=n_layers, channels_interval=16)             # trains: train()
     elif name == 'gradpeak':
         chirp = 'chirp' in str(cfg.data_dir).lower()
         model = GradPeak(threshold=cfg.th, rescale_factor=cfg.rf_scale_factor,
@@ -162,14 +162,14 @@ def main(argv=None):
     log = RunLog(cfg)
     if log.enabled and str(cfg.run_name) == 'local-run':
         cfg.run_name = log.name                                          # the reference names checkpoints after the wandb run
-    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name in ('stofnet', 'edsr', 'espcn', 'zonzini', 'sincnet')) else None
+    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name in ('stofnet', 'edsr', 'espcn', 'zonzini', 'sincnet', 'unet')) else None
     es_all, summary = evaluate(model, name, frames, gt, cfg, log)
     log.summary({'model_name': name, 'total_parameters': int(sum(p.numel() for p in model.parameters())),
                  'total_jaccard': summary.get('total_jaccard'), 'total_inference_time': summary['inference_time'],
                  'total_distance_mean': summary.get('total_distance_mean'), 'total_distance_std': summary.get('total_distance_std')})
     if history is not None:
         summary['train_history'] = history
-        if name in ('edsr', 'espcn', 'zonzini', 'sincnet'):
+        if name in ('edsr', 'espcn', 'zonzini', 'sincnet', 'unet'):
             summary['train_route'], summary['train_precision'] = model.train_route, 'fp32'
     if int(os.environ.get('RANK', '0')) == 0:
         print(json.dumps(summary))
@@ -214,7 +214,8 @@ def train(model, frames, gt, cfg, log=None):
     (model=zonzini) take the same lines and the same switch (stofnet_amd/zonzini_training.py) with `zonzini_loss` as their loss.
     SincNet (model=sincnet, upsample_factor 1) takes them too (stofnet_amd/sincnet_training.py): its BatchNorm layers run in train
     mode, so every step also updates their running statistics, and under DDP each rank normalises with its own batch statistics
-    (the reference has no SyncBatchNorm either).
+    (the reference has no SyncBatchNorm either).  WaveUnet (model=unet, upsample_factor 1) does the same through
+    stofnet_amd/waveunet_training.py.
 
     With `augment=True` every training batch goes through stofnet_amd.augment.Augment first (generator: seed = cfg.seed,
     rank = RANK, one `call` per step) and the ground truth moves with the crop window before it becomes sample indices.
@@ -230,7 +231,7 @@ def train(model, frames, gt, cfg, log=None):
     if world > 1 and not dist.is_initialized():
         dist.init_process_group('nccl', device_id=torch.device(cfg.device))
     zonzini = isinstance(model, (ZonziniNetSmall, ZonziniNetLarge))
-    routed = zonzini or isinstance(model, (EDSR_1D, ESPCN_1D, SincNet))          # the baselines with a `train_route` switch
+    routed = zonzini or isinstance(model, (EDSR_1D, ESPCN_1D, SincNet, WaveUnet))          # the baselines with a `train_route` switch
     tr = None if routed else StofNetTrainer(model, lr=cfg.lr, weight_decay=cfg.weight_decay, lambda_value=cfg.lambda_value,
                                             mask_amplitude=cfg.mask_amplitude, kernel_size=cfg.kernel_size, sigma=cfg.sigma,
                                             precision=cfg.train_precision)

@@ -208,6 +208,29 @@ _SIGNATURES = {
     'stof_waveunet_workspace_bytes': (_c.c_size_t, [_c.POINTER(WaveUnetDesc), _c.c_int64, _c.c_int64]),
     'stof_waveunet_forward': (_c.c_int, [_c.POINTER(WaveUnetDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
                                          _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_waveunet_train_constants': (_c.c_int, [_c.POINTER(_c.c_int64)]),
+    'stof_waveunet_interp_table': (_c.c_int, [_c.c_int64] + [_c.c_void_p] * 6),
+    'stof_waveunet_train_frag_floats': (_c.c_size_t, [_c.c_int32] * 4),
+    'stof_waveunet_train_pack_frag': (_c.c_int, [_c.c_void_p] + [_c.c_int32] * 4 + [_c.c_void_p] * 2),
+    'stof_waveunet_train_pack_in': (_c.c_int, [_c.c_void_p] * 4),
+    'stof_waveunet_train_in_conv': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_waveunet_train_conv': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64] + [_c.c_int32] * 5 + [_c.c_void_p] * 4),
+    'stof_waveunet_train_stats_workspace_bytes': (_c.c_size_t, []),
+    'stof_waveunet_train_stats': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32] + [_c.c_void_p] * 4 + [_c.c_double] * 2 +
+                                  [_c.c_void_p] * 4 + [_c.c_size_t, _c.c_void_p]),
+    'stof_waveunet_train_apply': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    'stof_waveunet_train_head': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64] + [_c.c_void_p] * 4),
+    'stof_waveunet_train_head_bwd_workspace_bytes': (_c.c_size_t, []),
+    'stof_waveunet_train_head_bwd': (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int64, _c.c_int64] + [_c.c_void_p] * 6 + [_c.c_size_t, _c.c_void_p]),
+    'stof_waveunet_train_bn_bwd': (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int64, _c.c_int32] + [_c.c_void_p] * 4 + [_c.c_size_t, _c.c_void_p]),
+    'stof_waveunet_train_wgrad_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int64] + [_c.c_int32] * 3),
+    'stof_waveunet_train_wgrad': (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int64, _c.c_int64] + [_c.c_int32] * 5 + [_c.c_void_p] * 3 +
+                                  [_c.c_size_t, _c.c_void_p]),
+    'stof_waveunet_train_in_wgrad_workspace_bytes': (_c.c_size_t, []),
+    'stof_waveunet_train_in_wgrad': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64] + [_c.c_void_p] * 3 + [_c.c_size_t, _c.c_void_p]),
+    'stof_waveunet_train_interp_t': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
+    'stof_waveunet_train_skip_sum': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
+    'stof_waveunet_train_in_dgrad': (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p]),
     'stof_kuleshov_packed_bytes': (_c.c_size_t, [_c.POINTER(KuleshovDesc)]),
     'stof_kuleshov_pack_weights': (_c.c_int, [_c.POINTER(KuleshovDesc), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_size_t]),
     'stof_kuleshov_workspace_bytes': (_c.c_size_t, [_c.POINTER(KuleshovDesc), _c.c_int64]),

@@ -12,6 +12,9 @@
 //
 // Activations are dense channel-last fp32, act[n][t][C], so the K span (tap, channel) of one output is contiguous.
 //
+// The kernels live in waveunet_net.h (shared with the training kernels of waveunet_train.hip); this file instantiates them with
+// the inference epilogue and holds the blob layout, the host packer and the forward.
+//
 //   wu_in_kernel     encoder 0 (Cin = 1) on the vector pipe, one thread per (position, 4 channels): folded bias, then taps
 //                    0 .. 14 as one fma chain, LeakyReLU.
 //   wu_conv_kernel   every other convolution as an implicit GEMM, templated on the tap count (15 | 5), the A source and
@@ -51,24 +54,14 @@
 #include <string.h>
 #include "mfma32_frag.h"
 #include "stof_common.h"
+#include "waveunet_net.h"
 
 namespace {
 
 using namespace stof_frag;
 
-constexpr int CI = 16;                     // channels_interval
-constexpr int MAX_LAYERS = 12;
-constexpr int TM = 64;                     // positions per work-group of wu_conv_kernel
-constexpr int CHUNK = 192;                 // channels per LDS pass
-constexpr int ENC_TAPS = 15, DEC_TAPS = 5;
-
 bool wu_desc_ok(const stof_waveunet_desc* d) {
     return d && d->channels_interval == CI && d->n_layers >= 1 && d->n_layers <= MAX_LAYERS;
-}
-
-int wu_ntw(int tiles) {
-    if (tiles <= 4) return tiles;
-    return (tiles % 4 == 0 || tiles % 3 != 0) ? 4 : 3;
 }
 
 struct WuConv {
@@ -129,172 +122,6 @@ WuWorkspace wu_workspace(int n, int64_t N, int64_t L) {
 
 bool wu_shape_ok(const stof_waveunet_desc* d, int64_t L) {
     return L >= 1 && L % ((int64_t)1 << d->n_layers) == 0;
-}
-
-__device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : 0.1f * v; }   // NaN takes the second arm and stays
-
-// ATen's fp32 source coordinates of the x2 linear interpolation with align_corners.  Contraction is off here: r has to be
-// the rounded product before i0 is subtracted (an fma would subtract from the exact one and move l1 by up to an ulp of r).
-__device__ __forceinline__ void wu_coords(float scale, int u, int M, int& i0, int& i1, float& l0, float& l1) {
-#pragma clang fp contract(off)
-    const float r = scale * (float)u;
-    i0 = (int)r;
-    if (i0 > M - 1) i0 = M - 1;
-    i1 = i0 + 1 < M ? i0 + 1 : M - 1;
-    l1 = r - (float)i0;
-    l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
-    l0 = 1.f - l1;
-}
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, acc) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (acc), 0, 0, 0)
-
-// --------------------------------------------------------------------------------------------------------- encoder 0
-// Thread o: flattened position m = o / 4 (m = n L + t), channels 4 (o % 4) .. + 3.
-__global__ __launch_bounds__(256) void wu_in_kernel(const float* __restrict__ x, long long M, long long L,
-                                                    const float* __restrict__ w, float* __restrict__ out) {
-    const long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= M * 4) return;
-    const long long m = o >> 2, t = m % L;
-    const int c = 4 * (int)(o & 3);
-    float4 acc = *reinterpret_cast<const float4*>(w + 15 * CI + c);
-#pragma unroll
-    for (int j = 0; j < ENC_TAPS; ++j) {
-        const long long u = t + j - 7;
-        const float xv = (u >= 0 && u < L) ? x[m + j - 7] : 0.f;
-        const float4 wv = *reinterpret_cast<const float4*>(w + j * CI + c);
-        acc.x = fmaf(wv.x, xv, acc.x);
-        acc.y = fmaf(wv.y, xv, acc.y);
-        acc.z = fmaf(wv.z, xv, acc.z);
-        acc.w = fmaf(wv.w, xv, acc.w);
-    }
-    *reinterpret_cast<float4*>(out + m * CI + c) = make_float4(leaky(acc.x), leaky(acc.y), leaky(acc.z), leaky(acc.w));
-}
-
-// ------------------------------------------------------------------------------------------------- implicit-GEMM convs
-struct WuConvArgs {
-    const float* src;                      // encoder source: the previous level [N, 2 Lout, Cin]; decoder: the skip [N, Lout, Cin - Cu]
-    const float* low;                      // decoder: the map to interpolate [N, Lout / 2, Cu]
-    const float4* frag;
-    const float* bias;
-    float* out;                            // [N, Lout, Cout]
-    long long Lout;
-    int tiles;                             // work-groups per waveform
-    int Cin, Cu, Cout, groups;
-    float scale;                           // decoder: float(M - 1) / float(2 M - 1), M = Lout / 2
-};
-
-// blockIdx.x = (waveform n, tile of TM positions), blockIdx.y = group of NTW N tiles.  LDS window row j holds position
-// t0 - PAD + j; lane (i = l & 15, q = l >> 4) of wave w reads rows 16 w + i + tap, channels 16 b + 4 q .. + 3.
-// C/D map of the MFMA: channel = lane & 15, position = 4 (lane >> 4) + r.
-template <int TAPS, bool DEC, int NTW>
-__global__ __launch_bounds__(256) void wu_conv_kernel(const WuConvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float win[];
-    constexpr int PAD = TAPS / 2, ROWS = TM + TAPS - 1;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 15, q = lane >> 4;
-    const long long n = blockIdx.x / a.tiles, t0 = (long long)(blockIdx.x % a.tiles) * TM;
-    const long long Lout = a.Lout;
-    const int nt0 = blockIdx.y * NTW;
-    const bool active = t0 + 16 * wave < Lout;          // a wave past the end of the waveform only takes part in the staging
-    const float4* bq = a.frag + (long long)nt0 * a.groups * 64 + lane;
-    f32x4 acc[NTW] = {};
-    int g = 0;
-    for (int c0 = 0; c0 < a.Cin; c0 += CHUNK) {
-        const int cw = a.Cin - c0 < CHUNK ? a.Cin - c0 : CHUNK, S = cw + 4, q4 = cw / 4;
-        if (c0) __syncthreads();
-        for (int idx = tid; idx < ROWS * q4; idx += 256) {
-            const int j = idx / q4, cl = 4 * (idx - j * q4), c = c0 + cl;
-            const long long u = t0 - PAD + j;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (u >= 0 && u < Lout) {
-                if constexpr (!DEC) {
-                    v = *reinterpret_cast<const float4*>(a.src + (n * 2 * Lout + 2 * u) * a.Cin + c);
-                } else if (c < a.Cu) {
-                    const long long M = Lout >> 1;
-                    int i0, i1;
-                    float l0, l1;
-                    wu_coords(a.scale, (int)u, (int)M, i0, i1, l0, l1);
-                    const float4 p0 = *reinterpret_cast<const float4*>(a.low + (n * M + i0) * a.Cu + c);
-                    const float4 p1 = *reinterpret_cast<const float4*>(a.low + (n * M + i1) * a.Cu + c);
-                    v = make_float4(l0 * p0.x + l1 * p1.x, l0 * p0.y + l1 * p1.y, l0 * p0.z + l1 * p1.z, l0 * p0.w + l1 * p1.w);
-                } else {
-                    const int Cs = a.Cin - a.Cu;
-                    v = *reinterpret_cast<const float4*>(a.src + (n * Lout + u) * Cs + (c - a.Cu));
-                }
-            }
-            *reinterpret_cast<float4*>(win + j * S + cl) = v;
-        }
-        __syncthreads();
-        const int blocks = cw / 16;
-        if (active) {
-            const float* ap = win + (16 * wave + i) * S + 4 * q;
-            for (int tap = 0; tap < TAPS; ++tap) {
-                for (int b = 0; b < blocks; ++b, ++g) {
-                    const float4 av = *reinterpret_cast<const float4*>(ap + tap * S + 16 * b);
-                    float4 bv[NTW];
-#pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt) bv[nt] = bq[((long long)nt * a.groups + g) * 64];
-#pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA16(av.x, bv[nt].x, acc[nt]);
-#pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA16(av.y, bv[nt].y, acc[nt]);
-#pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA16(av.z, bv[nt].z, acc[nt]);
-#pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt) acc[nt] = MFMA16(av.w, bv[nt].w, acc[nt]);
-                }
-            }
-        }
-    }
-    if (!active) return;
-#pragma unroll
-    for (int nt = 0; nt < NTW; ++nt) {
-        const int ch = 16 * (nt0 + nt) + i;
-        if (ch >= a.Cout) continue;
-        const float b = a.bias[ch];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const long long p = t0 + 16 * wave + 4 * q + r;
-            if (p < Lout) a.out[(n * Lout + p) * a.Cout + ch] = leaky(acc[nt][r] + b);
-        }
-    }
-}
-
-// -------------------------------------------------------------------------------------------------------------- head
-// Thread m = n L + t: bias, then the 16 decoder channels and x as one fma chain.
-__global__ __launch_bounds__(256) void wu_head_kernel(const float* __restrict__ o, const float* __restrict__ x, long long M,
-                                                      const float* __restrict__ w, float* __restrict__ y,
-                                                      float* __restrict__ logits) {
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= M) return;
-    float acc = w[CI + 1];
-#pragma unroll
-    for (int c = 0; c < CI; c += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(o + m * CI + c);
-        acc = fmaf(w[c], v.x, acc);
-        acc = fmaf(w[c + 1], v.y, acc);
-        acc = fmaf(w[c + 2], v.z, acc);
-        acc = fmaf(w[c + 3], v.w, acc);
-    }
-    acc = fmaf(w[CI], x[m], acc);
-    if (logits) logits[m] = acc;
-    y[m] = tanhf(acc);
-}
-
-template <int TAPS, bool DEC, int NTW>
-void launch_conv_ntw(dim3 grid, size_t lds, hipStream_t s, const WuConvArgs& a) {
-    hipLaunchKernelGGL((wu_conv_kernel<TAPS, DEC, NTW>), grid, dim3(256), lds, s, a);
-}
-
-template <int TAPS, bool DEC>
-void launch_conv(int ntw, dim3 grid, size_t lds, hipStream_t s, const WuConvArgs& a) {
-    switch (ntw) {
-        case 1: launch_conv_ntw<TAPS, DEC, 1>(grid, lds, s, a); break;
-        case 2: launch_conv_ntw<TAPS, DEC, 2>(grid, lds, s, a); break;
-        case 3: launch_conv_ntw<TAPS, DEC, 3>(grid, lds, s, a); break;
-        default: launch_conv_ntw<TAPS, DEC, 4>(grid, lds, s, a); break;
-    }
 }
 
 }  // namespace
@@ -377,7 +204,7 @@ extern "C" int stof_waveunet_forward(const stof_waveunet_desc* desc, const float
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t M = N * L;
 
-    hipLaunchKernelGGL(wu_in_kernel, dim3((unsigned)((M * 4 + 255) / 256)), dim3(256), 0, s, x, (long long)M, (long long)L,
+    hipLaunchKernelGGL(wu_in_kernel<true>, dim3((unsigned)((M * 4 + 255) / 256)), dim3(256), 0, s, x, (long long)M, (long long)L,
                        blob + o.enc0, base + ws.skip[0]);
     if (hipGetLastError() != hipSuccess) return STOF_ERR_HIP;
 
@@ -387,15 +214,12 @@ extern "C" int stof_waveunet_forward(const stof_waveunet_desc* desc, const float
         a.frag = reinterpret_cast<const float4*>(blob + c.frag);
         a.bias = blob + c.bias;
         a.Lout = Lout;
-        a.tiles = (int)((Lout + TM - 1) / TM);
-        a.Cin = c.cin; a.Cu = c.cu; a.Cout = c.cout; a.groups = c.groups;
-        const int64_t Mlow = Lout / 2;
-        a.scale = c.cu ? (float)(Mlow - 1) / (float)(2 * Mlow - 1) : 0.f;
-        const dim3 grid((unsigned)(N * a.tiles), (unsigned)(c.ntp / c.ntw));
-        const int cw = c.cin < CHUNK ? c.cin : CHUNK;
-        const size_t lds = sizeof(float) * (size_t)(TM + c.taps - 1) * (cw + 4);
-        if (c.cu) launch_conv<DEC_TAPS, true>(c.ntw, grid, lds, s, a);
-        else launch_conv<ENC_TAPS, false>(c.ntw, grid, lds, s, a);
+        a.Cin = c.cin; a.Cu = c.cu; a.Cout = c.cout;
+        dim3 grid;
+        size_t lds;
+        wu_conv_geometry(a, c.taps, N, c.ntw, c.ntp, grid, lds);
+        if (c.cu) wu_launch_conv<DEC_TAPS, SRC_DECODER, true>(c.ntw, grid, lds, s, a);
+        else wu_launch_conv<ENC_TAPS, SRC_DECIMATED, true>(c.ntw, grid, lds, s, a);
         return hipGetLastError() == hipSuccess;
     };
 
@@ -410,7 +234,7 @@ extern "C" int stof_waveunet_forward(const stof_waveunet_desc* desc, const float
         if (!conv(o.conv[k], base + ws.skip[n - 1 - i], low, out, L >> (n - 1 - i))) return STOF_ERR_HIP;
         low = out;
     }
-    hipLaunchKernelGGL(wu_head_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, low, x, (long long)M, blob + o.head, y,
-                       logits);
+    hipLaunchKernelGGL(wu_head_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, low, x, (long long)M, blob + o.head,
+                       blob + o.head + CI + 1, y, logits);
     return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP;
 }

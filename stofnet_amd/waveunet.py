@@ -1,16 +1,22 @@
 """Wave-U-Net, the reference's `unet` baseline (models/wave_unet.py:34-102; selected by main.py:44-46,159-160).
 
 Constructor arguments, module tree and parameter names follow the reference, so its checkpoints load with strict=True
-(`encoder.{i}.main.0|1.*`, `middle.0|1.*`, `decoder.{i}.main.0|1.*`, `out.0.*`).  Two routes, as for EDSR_1D / ESPCN_1D:
+(`encoder.{i}.main.0|1.*`, `middle.0|1.*`, `decoder.{i}.main.0|1.*`, `out.0.*`).  Three routes:
 
   forward_aten(x)     the reference's forward on stock ATen layers; it trains, and in train mode BatchNorm uses batch
                       statistics and updates its running ones;
   forward_kernels(x)  inference on the gfx950 kernels of csrc/waveunet.hip in exact fp32 with eval-mode BatchNorm folded
                       into the convolutions: one vector kernel for encoder 0, one implicit-GEMM kernel per other
                       convolution (the x2 decimation is a stride of its loads, the x2 linear interpolation and the
-                      concatenation with the skip are built in LDS), one vector kernel for the output convolution + tanh.
+                      concatenation with the skip are built in LDS), one vector kernel for the output convolution + tanh;
+  forward_train_kernels(x)  a train-mode step on the gfx950 training kernels (waveunet_training.py, csrc/waveunet_train.hip)
+                      behind an autograd boundary: batch statistics, running statistics updated, exact fp32 and bitwise
+                      repeatable gradients of every parameter (and of x when it asks for one).
 
-`forward` takes the kernels in eval mode when `kernels_supported(x)` holds and no autograd graph would be recorded.
+`forward` takes the inference kernels in eval mode when `kernels_supported(x)` holds and no autograd graph would be recorded.
+`train_route` (class default 'aten'; 'aten' | 'kernels', not part of the state_dict) decides train-mode calls: with 'aten' they
+go to `forward_aten` as every other call does, with 'kernels' to `forward_train_kernels`, graph or not, which raises where the
+kernels do not apply instead of falling back.  Eval-mode calls are the same under either setting.
 Served on the kernels: channels_interval = 16 (what main.py builds), n_layers 1 .. 12, L a multiple of 2^n_layers; another
 channels_interval raises NotImplementedError on construction.  The packed weights are cached per (device, storage,
 `_version`) of every parameter and of the BatchNorm running statistics; rows are bitwise independent of their batch, so
@@ -57,7 +63,8 @@ class WaveUnet(_KernelRoute, nn.Module):
     output convolution on (decoder output, input) with tanh."""
     max_workspace_bytes = 512 << 20
     _KERNEL_CONFIG = 'a length that is a multiple of 2^n_layers'
-    _EVAL_ONLY = True
+    _EVAL_ONLY = True       # the inference kernels serve eval mode only; train mode is decided by `train_route`
+    train_route = 'aten'    # 'aten' | 'kernels': what a train-mode call runs on
 
     def __init__(self, n_layers=12, channels_interval=24):
         super().__init__()
@@ -136,3 +143,44 @@ class WaveUnet(_KernelRoute, nn.Module):
             o = F.interpolate(o, scale_factor=2, mode='linear', align_corners=True)
             o = block(torch.cat([o, skips[self.n_layers - i - 1]], dim=1))
         return self.out(torch.cat([o, x], dim=1))
+
+    def forward_train_kernels(self, x):
+        """y [N, 1, L] float32 of a train-mode call on the gfx950 training kernels (waveunet_training.py), with an autograd
+        graph when one is recorded: its backward fills the gradient of every parameter (and of x, if it asks for one) in
+        exact fp32.  BatchNorm uses batch statistics and the running statistics are updated, also under no_grad.  Not
+        chunked by `max_workspace_bytes`: the batch statistics and the backward need every activation of the whole batch."""
+        from .waveunet_training import WaveUnetFunction, WaveUnetTrainEngine
+        if not self.training:
+            raise NotImplementedError("WaveUnet: train_route='kernels' serves train mode only (batch statistics); eval-mode "
+                                      'calls take the inference kernels or forward_aten')
+        self._check_kernels(x)
+        n = self.n_layers
+        N, L = int(x.shape[0]), int(x.shape[-1])
+        if N * (L >> n) == 1:                               # torch's BatchNorm check, word for word, before anything is touched
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size {torch.Size([N, 16 * n, L >> n])}')
+        bns = [blk.main[1] for blk in self.encoder] + [self.middle[1]] + [blk.main[1] for blk in self.decoder]
+        engines = self.__dict__.setdefault('_train_engines', {})
+        key = str(x.device)
+        if key not in engines:
+            engines[key] = WaveUnetTrainEngine(x.device, n)
+        engine = engines[key]
+        engine.eps = [float(bn.eps) for bn in bns]
+        engine.momentum = [float(bn.momentum) for bn in bns]
+        engine.running = [(bn.running_mean, bn.running_var) for bn in bns]
+        names, params = zip(*self.named_parameters())
+        y = WaveUnetFunction.apply(x, engine, names, *params)
+        if N:
+            with torch.no_grad():                # on the host side: `copy_` bumps the buffers' versions (the eval-mode blob's key)
+                for bn, (mean, var) in zip(bns, engine.new_running):
+                    bn.running_mean.copy_(mean)
+                    bn.running_var.copy_(var)
+                    bn.num_batches_tracked.add_(1)
+        return y
+
+    def forward(self, x):
+        route = self.train_route
+        if route not in ('aten', 'kernels'):
+            raise ValueError(f"WaveUnet.train_route must be 'aten' or 'kernels' (got {route!r})")
+        if route == 'kernels' and self.training:
+            return self.forward_train_kernels(x)
+        return super().forward(x)
