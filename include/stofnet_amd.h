@@ -788,7 +788,8 @@ int stof_train_pool_bwd(const float* gpool, const uint8_t* arg, const float* c, 
 
 /* Data gradient of conv_last (64 -> r channels, k3) on the vector pipe, exact fp32: out[N, L, 64] from dz[N, L, r] and
  * conv_last.weight in torch layout [r][64][3] = what stof_train_conv computes with the repacked data-gradient weights.
- * r = 4 or 10; otherwise STOF_ERR_UNSUPPORTED.                                                                        */
+ * r = 4 or 10; otherwise STOF_ERR_UNSUPPORTED.  `out` is written with 16-byte stores and must be 16-byte aligned (else
+ * STOF_ERR_BAD_ARG, here and in stof_train_conv_last_dgrad_split); dz and weight are read float by float: any fp32 pointer.  */
 int stof_train_conv_last_dgrad(const float* dz, const float* weight, float* out, int64_t N, int64_t L, int32_t r, void* stream);
 
 /* SemiGlobalBlock backward, contract_conv's weight / bias gradient straight from the pool's SPARSE gradient (one non-zero
@@ -884,7 +885,8 @@ int stof_train_add_split(const float* a_split, const float* b, float* out, int64
 /* The same with b a split-row tensor as well.                                                                              */
 int stof_train_add_split2(const float* a_split, const float* b_split, float* out, int64_t rows, void* stream);
 /* stof_train_conv_last_dgrad with out written as split rows: the g6 operand of stof_train_sweep_bwd_split (which expects its g6
- * as split rows) and of stof_train_wgrad_batch_split.                                                                      */
+ * as split rows) and of stof_train_wgrad_batch_split, which both need it 16-byte aligned: a misaligned `out` is
+ * STOF_ERR_BAD_ARG.                                                                                                        */
 int stof_train_conv_last_dgrad_split(const float* dz, const float* weight, float* out, int64_t N, int64_t L, int32_t r, void* stream);
 /* out = a + b (gradient joins of the residual / long-skip branches, models/stofnet.py:56,62).         */
 int stof_train_add(const float* a, const float* b, float* out, int64_t n, void* stream);

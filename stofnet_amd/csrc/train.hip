@@ -2441,6 +2441,7 @@ static int conv_last_dgrad_impl(const float* dz, const float* weight, float* out
     if (r != 4 && r != 10) return STOF_ERR_UNSUPPORTED;
     if (N == 0 || L == 0) return STOF_OK;
     if (!dz || !weight || !out) return STOF_ERR_BAD_ARG;
+    if (reinterpret_cast<size_t>(out) & 15) return STOF_ERR_BAD_ARG;      // written with 16-byte (fp32 rows) / 8-byte (split rows) stores
     const int64_t groups = N * ((L + CLD_ROWS - 1) / CLD_ROWS);
     if (groups > 0x7fffffffLL) return STOF_ERR_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);

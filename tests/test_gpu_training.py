@@ -409,7 +409,15 @@ def test_weight_gradient_routes_agree(dev, monkeypatch):
     (on 16x16x32 MFMAs: the default; on 32x32x16), its eight-wave form, split rows on the register-staged kernel, fp32 dumps -- and the first three feed the MFMAs the
     SAME fp16 hi / lo halves: the register-staged and the four-wave kernel sum them in the same order (bitwise equal weight
     gradients), the eight-wave form groups a tile's K-steps differently (1e-5); the fp32-dump route differs only in the leaky-ReLU
-    mask of activations below 2^-25 and in the bias sums' order.  All of them against the reference golden."""
+    mask of activations below 2^-25 and in the bias sums' order.  All of them against the reference golden.
+
+    WHAT RUNS HERE, on a 256-CU device: at 8 x 2000 the launch cuts every waveform into 8 segments of 250 + 76 + 4 = 330 stream
+    rows, below the 384 the two-pass sweep kernel needs, so stof_train_sweep_split answers STOF_ERR_UNSUPPORTED and the step runs
+    the r3 sweep kernel with fp32 dumps and stof_train_wgrad_batch on fp32 operands under EVERY one of the five settings: the
+    "routes" above are one route there, and the comparisons below compare it with itself.  They stay as a check that the
+    switches are harmless at this shape.  The routes themselves -- each kernel form on split rows, and the whole step with these
+    switches at shapes where the engine does take split dumps -- are tested in tests/test_gpu_split_route.py
+    (test_wgrad_batch_split_second_tile_exact, test_whole_step_on_the_split_route)."""
     from conftest import golden
     g = golden('f8_training_c5')
     frame = torch.from_numpy(synth.synth_echo(8, 2000, seed=3008)).to(dev)
