@@ -360,6 +360,17 @@ def check(code: int, what: str = ''):
     raise ValueError(msg)
 
 
+def call(name: str, *args):
+    """Entry `name` of the library on plain Python arguments: a ctypes structure goes by reference, a tensor as its device
+    pointer, None (a NULL pointer), numbers and ctypes arrays as they are.  An int result is a stof_status and is checked under
+    `name`; any other result (a size) is returned."""
+    fn = getattr(lib(), name)
+    out = fn(*[ptr(a) if isinstance(a, torch.Tensor) else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a for a in args])
+    if _SIGNATURES[name][0] is not ctypes.c_int:
+        return out
+    check(out, name)
+
+
 def require_device(t: torch.Tensor, name: str = 'tensor') -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f'{name} must be a torch.Tensor')

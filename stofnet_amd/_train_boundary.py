@@ -5,7 +5,11 @@ their kernels, and `carve_grads`, which StofNet's own boundary (`training.StofNe
   SavedStepEngine  the base of an engine with `_forward_saved(p, frame) -> (y [N, out columns], saved)` and
                    `_backward_saved(saved, dy, g, dx)`: the frame flattening, the check that no parameter changed between
                    the two, and the cache of kernel-layout weight images
-  EndsFunction     the autograd boundary over such an engine"""
+                   and of the packed blob of all parameters
+  EndsFunction     the autograd boundary over such an engine
+  fp32_device_params, train_engine, commit_running_stats   what the models' `forward_train_kernels` do around the boundary"""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -24,6 +28,34 @@ def carve_grads(names, shapes, dev):
     return flat, g
 
 
+def fp32_device_params(module, label):
+    """(names, parameters) of `module`, every parameter checked to be float32 on a ROCm device"""
+    names, params = zip(*module.named_parameters())
+    for p in params:
+        if p.dtype != torch.float32:
+            raise TypeError(f'{label}: parameters must be float32 (got {p.dtype}); the gfx950 kernels are fp32 only')
+        _lib.require_device(p, 'parameter')
+    return names, params
+
+
+def train_engine(module, key, make):
+    """The training engine of `module` under `key` (the device and whatever else an engine is built for), made on first use."""
+    engines = module.__dict__.setdefault('_train_engines', {})
+    if key not in engines:
+        engines[key] = make()
+    return engines[key]
+
+
+def commit_running_stats(bns, new_running):
+    """The new running statistics of a train-mode forward into the BatchNorm modules' buffers, on the host side: `copy_` bumps
+    the buffers' versions, which are the eval-mode blob's key."""
+    with torch.no_grad():
+        for bn, (mean, var) in zip(bns, new_running):
+            bn.running_mean.copy_(mean)
+            bn.running_var.copy_(var)
+            bn.num_batches_tracked.add_(1)
+
+
 class SavedStepEngine(LayerKernels):
     """Exact fp32 `LayerKernels` of one model (`label`: its name in messages, `r`: its upscale factor) on one device."""
     label = None
@@ -32,6 +64,7 @@ class SavedStepEngine(LayerKernels):
         super().__init__(dev, _lib.PREC_FP32)
         self.r = int(r)
         self._images = {}           # key -> ((data_ptr, _version) of the weight, its kernel-layout image)
+        self._blob = None           # ((data_ptr, _version) of every packed parameter, the blob of the forward kernels)
 
     def out_shape(self, n, L):
         """shape of `model(frame)` for a frame [n, 1, L]: the upsampled row of the SampleShuffle1D nets"""
@@ -57,6 +90,17 @@ class SavedStepEngine(LayerKernels):
         if hit is None or hit[0] != version:
             hit = self._images[key] = (version, make())
         return hit[1]
+
+    def _packed_blob(self, p, names, nbytes, entry, desc):
+        """The forward kernels' blob of this step's parameters `names`, packed on the device by `entry` (into the same buffer)
+        again when one of them changed."""
+        version = tuple((p[k].data_ptr(), p[k]._version) for k in names)
+        if self._blob is None or self._blob[0] != version:
+            blob = self._blob[1] if self._blob is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+            ptrs = (ctypes.c_void_p * len(names))(*[p[k].data_ptr() for k in names])
+            _lib.call(entry, desc, ptrs, blob, nbytes, self._st())
+            self._blob = (version, blob)
+        return self._blob[1]
 
 
 class EndsFunction(torch.autograd.Function):

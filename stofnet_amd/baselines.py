@@ -31,6 +31,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._kernel_route import _KernelRoute, _pack
+from ._train_boundary import train_engine
 from .edsr_training import EdsrFunction, EdsrTrainEngine
 from .espcn_training import EspcnFunction, EspcnTrainEngine
 from .sample_shuffle import SampleShuffle1D
@@ -67,12 +68,10 @@ class _TrainRoute(_KernelRoute):
         """y [N, 1, L r] float32 on the gfx950 training kernels, with an autograd graph: its backward fills the gradient of
         every parameter (and of x, if it asks for one) in exact fp32; raises where the kernels do not apply."""
         self._check_kernels(x)
-        engines = self.__dict__.setdefault('_train_engines', {})
         key = (str(x.device), *self._train_engine_key())
-        if key not in engines:
-            engines[key] = self._make_train_engine(x.device, key[1:])
+        engine = train_engine(self, key, lambda: self._make_train_engine(x.device, key[1:]))
         names, params = zip(*self.named_parameters())
-        return self._train_function.apply(x, engines[key], names, *params)
+        return self._train_function.apply(x, engine, names, *params)
 
     def forward(self, x):
         if self.train_route not in ('aten', 'kernels'):

@@ -3,7 +3,7 @@
 // end is a predicate, so the zero padding of conv2 and conv3 is zeros of h1 and h2 (not tanh(bias)).
 //
 //   ep_in_kernel          h1 = tanh(conv1(x)), 1 -> 64, k 5                          (vector pipe)
-//   ep_repack_kernel      conv2.weight (32,64,3) -> the B-operand fragment image of ep_mid_kernel
+//   pack_frag32_kernel    (mfma32_frag.h) conv2.weight (32,64,3) -> the B-operand fragment image of ep_mid_kernel
 //   ep_mid_kernel         h2 = tanh(conv2(h1) + b2), 64 -> 32, k 3                   (v_mfma_f32_32x32x2_f32)
 //   ep_out_kernel         y = sigmoid(conv3(h2) + b3), 32 -> r, k 3                  (vector pipe)
 //   ep_out_wgrad_kernel   dW3 (r,32,3), db3 (r) from dz = dy y (1 - y) and h2
@@ -77,16 +77,8 @@ __global__ __launch_bounds__(256) void ep_in_dgrad_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------------- conv2
-// conv2.weight in torch layout (32,64,3) -> [24 K groups][64 lanes][4] in the fragment order of mfma32_frag.h with
-// k = tap * 64 + ci: lane (i = l & 31, h = l >> 5), element e of group q holds W[i][k = 8 q + 4 h + e].
-__global__ __launch_bounds__(256) void ep_repack_kernel(const float* __restrict__ w, float* __restrict__ out) {
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= PM_GROUPS * 256) return;
-    const int e = o & 3, lane = (o >> 2) & 63, q = o >> 8;
-    const int k = 8 * q + 4 * (lane >> 5) + e, tap = k / C1, ci = k % C1;
-    out[o] = w[((lane & 31) * C1 + ci) * 3 + tap];
-}
-
+// conv2.weight in torch layout (32,64,3) is packed by pack_frag32_kernel of mfma32_frag.h: one N tile of [24 K groups][64 lanes][4]
+// with k = tap * 64 + ci.
 // A work-group stages flat rows r0 - 1 .. r0 + PM_TILE of h1 in LDS (row j = flat row r0 - 1 + j, zero outside the buffer) and
 // wave w computes rows r0 + 32 w .. + 31: the A operand of lane (i, h) is the float4 at channel 8 (q & 7) + 4 h of row i + tap,
 // zeroed where that tap crosses the end of row i's waveform; the 32 output channels are the one N tile.  Eight accumulators,
@@ -328,7 +320,7 @@ extern "C" size_t stof_train_espcn_repack_floats(void) { return (size_t)PM_GROUP
 
 extern "C" int stof_train_espcn_repack(const float* w2, float* out, void* stream) {
     if (!w2 || !out) return STOF_ERR_BAD_ARG;
-    hipLaunchKernelGGL(ep_repack_kernel, dim3(PM_GROUPS), dim3(256), 0, static_cast<hipStream_t>(stream), w2, out);
+    stof_frag::pack_frag32_device(static_cast<hipStream_t>(stream), w2, 32, C1, 3, C1, PM_GROUPS, out, PM_GROUPS * 256);
     return launched();
 }
 

@@ -3,14 +3,9 @@
 // one-channel tensors of layer 3 (z_3, y, dy, dz_3) are flat [N L].
 //
 //   forward, per layer    the kernels of sincnet_net.h with EPI_BIAS: the raw pre-BatchNorm z_l = conv + bias;
-//                         sn_stats_partial_kernel + sn_stats_final_kernel: per channel the sum and the sum of squares over the
-//                         N L rows in double from the first addition (one partial per row chunk, folded in chunk order), then
-//                         mean, biased variance, rstd, s = gamma rstd, t = beta - mean s in double, and the new running
-//                         statistics (momentum, unbiased variance) into temporaries;
-//                         sn_apply_kernel: a_l = leaky(z_l s + t), layer 3: y = z_3 s + t, the affine in double, rounded once.
-//   backward, per layer   sn_bnb_partial_kernel + sn_bnb_final_kernel: sum g and sum g xhat per channel (double partials, fixed
-//                         fold) with g = da (a > 0 ? 1 : 0.2) and xhat = (z - mean) rstd -> dgamma, dbeta;
-//                         sn_dz_kernel: dz = s (g - sum g / M - xhat sum(g xhat) / M);
+//                         the train-mode BatchNorm of bn_train.h (statistics, a_l = leaky(z_l s + t), layer 3: y = z_3 s + t)
+//                         with the view and the activation below (GapRows, SincAct).
+//   backward, per layer   bn_train.h again: dgamma, dbeta and dz with g = da (a > 0 ? 1 : 0.2);
 //                         data gradient of layers 1, 2: sn_conv_kernel with EPI_NONE on the flipped, transposed image;
 //                         sn_wgrad_kernel (v_mfma_f32_32x32x2_f32): dW[co][tap 128 + ci] = sum over rows of dz[row][co]
 //                         a_prev[row + tap - P][ci], the reduction dimension is the rows; db in a bias slot of the partial;
@@ -20,8 +15,8 @@
 //                         (one work-group per filter); sn_in_dgrad_kernel: dx on the vector pipe, on request only.
 //   packing               (stof_sincnet_device_pack builds the INFERENCE blob from the same kernels plus sn_pack_affine_kernel)
 //                         sn_pack_bank_kernel synthesises the bank in double straight into fragment order (and as bank_t
-//                         [tap][filter] for dx), sn_pack_frag_kernel the conv images (flipped for the data gradient),
-//                         sn_pack_w3_kernel w3 [tap][ci].
+//                         [tap][filter] for dx), pack_frag32_kernel of mfma32_frag.h the conv images, sn_dgrad_image_kernel
+//                         the flipped ones of the data gradient, sn_pack_w3_kernel w3 [tap][ci].
 //
 // No float atomics and no library call.  Rows (bank gradient: 128-sample tiles) are cut into contiguous chunks, at most
 // *_MAX_COPIES of them, so above *_CHUNK x *_MAX_COPIES rows (64 tiles) a chunk grows: a work-group then walks more rows, and
@@ -29,6 +24,7 @@
 // writes one partial (there is no grid-stride loop over chunks); partial_reduce adds the partials.  Every sum's order depends on the shape alone, so two runs are bitwise equal.
 #include <stdint.h>
 #include "sincnet_net.h"
+#include "bn_train.h"
 #include "wgrad_reduce.h"
 
 namespace {
@@ -41,21 +37,11 @@ constexpr int BG_MAX_COPIES = 64;        // partials of sn_bank_grad_kernel (a c
 constexpr int ST_CHUNK = 256;            // rows per partial of the statistics kernels, at the least
 constexpr int ST_MAX_COPIES = 1024;
 
-inline int launched() { return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP; }
-
 inline int dims_ok(int64_t N, int64_t L) {
     if (N <= 0 || L <= 0) return STOF_ERR_BAD_ARG;
     if (N * L >= (1ll << 31) - 64 || N * (L + GAP) + GAP >= (1ll << 31) - 64) return STOF_ERR_UNSUPPORTED;   // 32-bit rows
     if ((N * (L + GAP) + GAP) * C >= (1ll << 40)) return STOF_ERR_UNSUPPORTED;
     return STOF_OK;
-}
-
-struct Chunks { int copies, per; };
-inline Chunks chunks_of(int64_t M, int chunk, int max_copies) {
-    int64_t c = (M + chunk - 1) / chunk;
-    if (c > max_copies) c = max_copies;
-    const int64_t per = (M + c - 1) / c;
-    return {(int)((M + per - 1) / per), (int)per};
 }
 
 // Blob of the training kernels (floats): frag0, frag1, frag2 as in the inference blob, bank_t [1024][128] (row 1023 zero),
@@ -75,12 +61,13 @@ inline TrainLayout train_layout() {
     return o;
 }
 
-// element index of (flat row m, channel c): GAP layout for CC = 128, flat for CC = 1
-template <int CC>
-__device__ __forceinline__ long long at_of(int m, int L, int c) {
-    if (CC == 1) return m;
-    return ((long long)GAP + (long long)(m / L) * GAP + m) * C + c;
-}
+// the 128-channel tensors as a view of bn_train.h: row m = n L + t of the GAP layout
+struct GapRows {
+    int L;
+    __host__ __device__ int channels() const { return C; }
+    __device__ long long at(long long m, int c) const { return ((long long)GAP + (long long)((int)m / L) * GAP + m) * C + c; }
+    __device__ void split(long long e, long long& m, int& c) const { m = e / C; c = (int)(e % C); }
+};
 
 // ------------------------------------------------------------------------------------------------------------- packing
 __global__ __launch_bounds__(256) void sn_pack_bank_kernel(double fs, const float* __restrict__ low_hz, const float* __restrict__ band_hz,
@@ -109,17 +96,20 @@ __global__ __launch_bounds__(256) void sn_pack_bank_kernel(double fs, const floa
     }
 }
 
-// pack_frag32 of mfma32_frag.h for a conv weight (128, 128, KT) with k = tap * 128 + c.  flip = 0: the forward image, row oc =
-// output channel, W[oc][c][tap].  flip = 1: the data gradient's image, row oc = INPUT channel, W[c][oc][KT - 1 - tap].
-__global__ __launch_bounds__(256) void sn_pack_frag_kernel(const float* __restrict__ w, int KT, int flip, float* __restrict__ out, int total) {
+// The forward image of a conv weight (128, 128, KT) is pack_frag32 of mfma32_frag.h with k = tap * 128 + c.  This is the data
+// gradient's image in the same order: row oc = INPUT channel, W[c][oc][KT - 1 - tap].
+__global__ __launch_bounds__(256) void sn_dgrad_image_kernel(const float* __restrict__ w, int KT, float* __restrict__ out, int total) {
     const int o = blockIdx.x * 256 + threadIdx.x;
     if (o >= total) return;
-    const int e = o & 3, lane = (o >> 2) & 63, rest = o >> 8;
-    const int groups = KT * C / 8;
-    const int q = rest % groups, nt = rest / groups;
-    const int oc = 32 * nt + (lane & 31), k = 8 * q + 4 * (lane >> 5) + e;
+    int nt, oc, k;
+    frag_decode(o, KT * C / 8, nt, oc, k);
     const int tap = k / C, c = k - tap * C;
-    out[o] = flip ? w[((size_t)c * C + oc) * KT + (KT - 1 - tap)] : w[((size_t)oc * C + c) * KT + tap];
+    out[o] = w[((size_t)c * C + oc) * KT + (KT - 1 - tap)];
+}
+
+// the forward image of conv.1 / conv.2
+inline void pack_conv_frag(hipStream_t s, const float* w, int KT, float* out) {
+    pack_frag32_device(s, w, C, C, KT, C, KT * C / 8, out, C * KT * C);
 }
 
 __global__ __launch_bounds__(256) void sn_pack_w3_kernel(const float* __restrict__ w, float* __restrict__ out) {
@@ -151,134 +141,18 @@ __global__ __launch_bounds__(256) void sn_gaps1_kernel(float* __restrict__ b, lo
     b[g * (L + GAP) * C + w] = 0.f;
 }
 
-// ---------------------------------------------------------------------------------------------------------- statistics
-// Thread (channel c = tid % CC, part = tid / CC) walks rows part, part + PARTS, ... of the chunk with two double chains (v and
-// v w, w = v for the batch statistics); part 0 adds the parts in order.  part [chunk][2][CC].
-template <int CC, class Row>
-__device__ __forceinline__ void chunk_sums(Row row, int M, int rows_per, double* __restrict__ part) {
-    constexpr int PARTS = 256 / CC;
-    __shared__ double red[2][256];
-    const int c = threadIdx.x % CC, p = threadIdx.x / CC;
-    const int m_begin = blockIdx.x * rows_per;
-    const int m_end = m_begin + rows_per < M ? m_begin + rows_per : M;
-    double s = 0.0, q = 0.0;
-    for (int m = m_begin + p; m < m_end; m += PARTS) {
-        float v, w;
-        row(m, c, v, w);
-        s += (double)v;
-        q += (double)v * (double)w;
-    }
-    red[0][threadIdx.x] = s;
-    red[1][threadIdx.x] = q;
-    __syncthreads();
-    if (p != 0) return;
-    for (int k = 1; k < PARTS; ++k) {
-        s += red[0][k * CC + c];
-        q += red[1][k * CC + c];
-    }
-    part[((size_t)blockIdx.x * 2 + 0) * CC + c] = s;
-    part[((size_t)blockIdx.x * 2 + 1) * CC + c] = q;
-}
-
-template <int CC>
-__global__ __launch_bounds__(256) void sn_stats_partial_kernel(const float* __restrict__ z, int M, int L, int rows_per,
-                                                               double* __restrict__ part) {
-    chunk_sums<CC>([&](int m, int c, float& v, float& w) { v = w = z[at_of<CC>(m, L, c)]; }, M, rows_per, part);
-}
-
-// stat [4][CC] doubles: mean, rstd, s = gamma rstd and t = beta - mean s
-template <int CC>
-__global__ __launch_bounds__(128) void sn_stats_final_kernel(const double* __restrict__ part, int copies, int M, double eps, double momentum,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             const float* __restrict__ run_mean, const float* __restrict__ run_var,
-                                                             double* __restrict__ stat, float* __restrict__ new_mean,
-                                                             float* __restrict__ new_var) {
-    const int c = threadIdx.x;
-    if (c >= CC) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < copies; ++k) {
-        s += part[((size_t)k * 2 + 0) * CC + c];
-        q += part[((size_t)k * 2 + 1) * CC + c];
-    }
-    const double mean = s / M;
-    double var = q / M - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + eps);
-    const double sc = (double)gamma[c] * rstd;
-    stat[c] = mean;
-    stat[CC + c] = rstd;
-    stat[2 * CC + c] = sc;
-    stat[3 * CC + c] = (double)beta[c] - mean * sc;
-    new_mean[c] = (float)((1.0 - momentum) * (double)run_mean[c] + momentum * mean);
-    new_var[c] = (float)((1.0 - momentum) * (double)run_var[c] + momentum * (var * M / (M - 1.0)));
-}
-
-template <int CC>
-__global__ __launch_bounds__(256) void sn_apply_kernel(const float* __restrict__ z, long long total, int L, const double* __restrict__ stat,
-                                                       float* __restrict__ out) {
-    const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (o >= total) return;
-    const int m = (int)(o / CC), c = (int)(o - (long long)m * CC);
-    const long long at = at_of<CC>(m, L, c);
-    // the affine in double, rounded once: t = beta - mean s carries mean s, which an fp32 z s + t would not cancel again where the
-    // batch variance is small (measured 2.7e-6 of max|a| at N L = 2 on Gaussian z)
-    const float v = (float)fma((double)z[at], stat[2 * CC + c], stat[3 * CC + c]);
-    out[at] = CC == 1 ? v : leaky(v);
-}
-
-// ------------------------------------------------------------------------------------------------- BatchNorm, backward
-// g = da times the LeakyReLU slope by the decision a > 0 (layer 3, a = NULL: g = da); xhat = (z - mean) rstd in double
-template <int CC>
-__device__ __forceinline__ void g_xhat(const float* da, const float* a, const float* z, const double* stat, int m, int L, int c, float& g,
-                                       double& xh) {
-    const long long at = at_of<CC>(m, L, c);
-    g = da[at];
-    if (CC != 1) g = a[at] > 0.f ? g : 0.2f * g;
-    xh = ((double)z[at] - stat[c]) * stat[CC + c];
-}
-
-template <int CC>
-__global__ __launch_bounds__(256) void sn_bnb_partial_kernel(const float* __restrict__ da, const float* __restrict__ a,
-                                                             const float* __restrict__ z, const double* __restrict__ stat, int M, int L,
-                                                             int rows_per, double* __restrict__ part) {
-    chunk_sums<CC>([&](int m, int c, float& v, float& w) {
-        double xh;
-        g_xhat<CC>(da, a, z, stat, m, L, c, v, xh);
-        w = (float)xh;
-    }, M, rows_per, part);
-}
-
-// coef [2][CC] doubles: sum g / M, sum g xhat / M
-template <int CC>
-__global__ __launch_bounds__(128) void sn_bnb_final_kernel(const double* __restrict__ part, int copies, int M, float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta, double* __restrict__ coef) {
-    const int c = threadIdx.x;
-    if (c >= CC) return;
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < copies; ++k) {
-        s += part[((size_t)k * 2 + 0) * CC + c];
-        q += part[((size_t)k * 2 + 1) * CC + c];
-    }
-    dbeta[c] = (float)s;
-    dgamma[c] = (float)q;
-    coef[c] = s / M;
-    coef[CC + c] = q / M;
-}
-
-template <int CC>
-__global__ __launch_bounds__(256) void sn_dz_kernel(const float* __restrict__ da, const float* __restrict__ a, const float* __restrict__ z,
-                                                    const double* __restrict__ stat, const double* __restrict__ coef,
-                                                    const float* __restrict__ gamma, long long total, int L, float* __restrict__ dz) {
-    const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (o >= total) return;
-    const int m = (int)(o / CC), c = (int)(o - (long long)m * CC);
-    float g;
-    double xh;
-    g_xhat<CC>(da, a, z, stat, m, L, c, g, xh);
-    xh = (double)(float)xh;                                      // the value the reductions saw
-    const double sc = (double)gamma[c] * stat[CC + c];
-    dz[at_of<CC>(m, L, c)] = (float)(sc * ((double)g - coef[c] - xh * coef[CC + c]));
-}
+// ----------------------------------------------------------------------------------------------------------- BatchNorm
+// What SincNet brings to bn_train.h.  Layers 0..2: SincAct<true> on the GAP layout, four channels per thread, two row parts
+// per channel; layer 3: SincAct<false> (no activation, `a` is not read) on the flat tensor, 256 row parts.  Both fold their
+// parts in ascending order and cut the rows by the balanced rule.
+template <bool LEAKY>
+struct SincAct {
+    static constexpr bool reads_a = LEAKY;
+    __device__ static double g(float da, float a) { return (double)(LEAKY ? (a > 0.f ? da : 0.2f * da) : da); }     // the slope in fp32
+    __device__ static double seen(double xh) { return (double)(float)xh; }                                          // xhat rounded to fp32
+    __device__ static double scale(const float* gamma, const double* stat, int C, int c) { return (double)gamma[c] * stat[C + c]; }
+    __device__ static float out(double u) { return LEAKY ? leaky((float)u) : (float)u; }
+};
 
 // ------------------------------------------------------------------------------------------ weight gradient, layers 1, 2
 // grid (chunk, KT, 4 co tiles); wave w of a work-group takes k tile 4 blockIdx.y + w (KT * 4 tiles of 32: all full).  MFMA
@@ -370,7 +244,7 @@ __global__ __launch_bounds__(256) void sn_out_dgrad_kernel(const float* __restri
         const int tt = t - j + 3;
         if (tt >= 0 && tt < L) acc = fmaf(w[ci * K3 + j], dz3[(long long)n * L + tt], acc);
     }
-    da2[at_of<C>(m, L, ci)] = acc;
+    da2[GapRows{L}.at(m, ci)] = acc;
 }
 
 // --------------------------------------------------------------------------------------------------- layer 0, backward
@@ -461,31 +335,6 @@ __global__ __launch_bounds__(256) void sn_in_dgrad_kernel(const float* __restric
     if (threadIdx.x == 0) dx[m] = red[0];
 }
 
-template <int CC>
-int stats_launch(hipStream_t s, const float* z, int M, int L, double eps, double momentum, const float* gamma, const float* beta,
-                 const float* run_mean, const float* run_var, double* stat, float* new_mean, float* new_var, double* part) {
-    const Chunks ch = chunks_of(M, ST_CHUNK, ST_MAX_COPIES);
-    hipLaunchKernelGGL(sn_stats_partial_kernel<CC>, dim3((unsigned)ch.copies), dim3(256), 0, s, z, M, L, ch.per, part);
-    if (launched() != STOF_OK) return STOF_ERR_HIP;
-    hipLaunchKernelGGL(sn_stats_final_kernel<CC>, dim3(1), dim3(128), 0, s, part, ch.copies, M, eps, momentum, gamma, beta, run_mean,
-                       run_var, stat, new_mean, new_var);
-    return launched();
-}
-
-template <int CC>
-int bnb_launch(hipStream_t s, const float* da, const float* a, const float* z, const double* stat, const float* gamma, int M, int L,
-               float* dgamma, float* dbeta, float* dz, double* part) {
-    const Chunks ch = chunks_of(M, ST_CHUNK, ST_MAX_COPIES);
-    double* coef = part + (size_t)ST_MAX_COPIES * 2 * CC;
-    hipLaunchKernelGGL(sn_bnb_partial_kernel<CC>, dim3((unsigned)ch.copies), dim3(256), 0, s, da, a, z, stat, M, L, ch.per, part);
-    if (launched() != STOF_OK) return STOF_ERR_HIP;
-    hipLaunchKernelGGL(sn_bnb_final_kernel<CC>, dim3(1), dim3(128), 0, s, part, ch.copies, M, dgamma, dbeta, coef);
-    if (launched() != STOF_OK) return STOF_ERR_HIP;
-    const long long total = (long long)M * CC;
-    hipLaunchKernelGGL(sn_dz_kernel<CC>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, da, a, z, stat, coef, gamma, total, L, dz);
-    return launched();
-}
-
 int zero_gaps(hipStream_t s, float* buf, int64_t N, int64_t L) {
     const int64_t gaps = (N + 1) * GAP * C;
     hipLaunchKernelGGL(sn_gaps1_kernel, dim3((unsigned)((gaps + 255) / 256)), dim3(256), 0, s, buf, (long long)L, (long long)gaps);
@@ -518,9 +367,8 @@ extern "C" int stof_sincnet_train_pack(const stof_sincnet_desc* desc, const floa
     if (hipMemsetAsync(blob, 0, (size_t)o.total * sizeof(float), s) != hipSuccess) return STOF_ERR_HIP;
     hipLaunchKernelGGL(sn_pack_bank_kernel, dim3((C * (HALF0 + 1) + 255) / 256), dim3(256), 0, s, desc->fs, params[0], params[1],
                        blob + o.frag0, blob + o.bank_t);
-    const int t1 = C * K1 * C, t2 = C * K2 * C;
-    hipLaunchKernelGGL(sn_pack_frag_kernel, dim3((t1 + 255) / 256), dim3(256), 0, s, params[2], K1, 0, blob + o.frag1, t1);
-    hipLaunchKernelGGL(sn_pack_frag_kernel, dim3((t2 + 255) / 256), dim3(256), 0, s, params[3], K2, 0, blob + o.frag2, t2);
+    pack_conv_frag(s, params[2], K1, blob + o.frag1);
+    pack_conv_frag(s, params[3], K2, blob + o.frag2);
     hipLaunchKernelGGL(sn_pack_w3_kernel, dim3((K3 * C + 255) / 256), dim3(256), 0, s, params[4], blob + o.w3);
     return launched();
 }
@@ -538,9 +386,8 @@ extern "C" int stof_sincnet_device_pack(const stof_sincnet_desc* desc, const flo
     if (hipMemsetAsync(blob, 0, (size_t)o.total * sizeof(float), s) != hipSuccess) return STOF_ERR_HIP;
     hipLaunchKernelGGL(sn_pack_bank_kernel, dim3((C * (HALF0 + 1) + 255) / 256), dim3(256), 0, s, desc->fs, params[0], params[1],
                        blob + o.frag0, (float*)nullptr);
-    const int t1 = C * K1 * C, t2 = C * K2 * C;
-    hipLaunchKernelGGL(sn_pack_frag_kernel, dim3((t1 + 255) / 256), dim3(256), 0, s, params[2], K1, 0, blob + o.frag1, t1);
-    hipLaunchKernelGGL(sn_pack_frag_kernel, dim3((t2 + 255) / 256), dim3(256), 0, s, params[4], K2, 0, blob + o.frag2, t2);
+    pack_conv_frag(s, params[2], K1, blob + o.frag1);
+    pack_conv_frag(s, params[4], K2, blob + o.frag2);
     hipLaunchKernelGGL(sn_pack_w3_kernel, dim3((K3 * C + 255) / 256), dim3(256), 0, s, params[6], blob + o.w3);
     const int64_t st_at[4] = {o.st0, o.st1, o.st2, o.st3};
     for (int l = 0; l < 4; ++l) {                                 // params 8 + 4 l ..: bn.l weight, bias, running_mean, running_var
@@ -556,7 +403,7 @@ extern "C" int stof_sincnet_device_pack(const stof_sincnet_desc* desc, const flo
 extern "C" int stof_sincnet_train_dgrad_image(int32_t layer, const float* w, float* out, void* stream) {
     if ((layer != 1 && layer != 2) || !w || !out) return STOF_ERR_BAD_ARG;
     const int KT = layer == 1 ? K1 : K2, total = C * KT * C;
-    hipLaunchKernelGGL(sn_pack_frag_kernel, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w, KT, 1, out, total);
+    hipLaunchKernelGGL(sn_dgrad_image_kernel, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w, KT, out, total);
     return launched();
 }
 
@@ -633,9 +480,12 @@ extern "C" int stof_sincnet_train_stats(const stof_sincnet_desc* desc, const flo
     if (workspace_bytes < stof_sincnet_train_stats_workspace_bytes()) return STOF_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
+    const Chunks ch = balanced_chunks(N * L, ST_CHUNK, ST_MAX_COPIES, 1);
     if (channels == C)
-        return stats_launch<C>(s, z, (int)(N * L), (int)L, desc->bn_eps, momentum, gamma, beta, run_mean, run_var, stat, new_mean, new_var, part);
-    return stats_launch<1>(s, z, (int)(N * L), (int)L, desc->bn_eps, momentum, gamma, beta, run_mean, run_var, stat, new_mean, new_var, part);
+        return bn_stats_launch<C, FoldAscending>(s, z, N * L, GapRows{(int)L}, ch, desc->bn_eps, momentum, gamma, beta, run_mean, run_var, stat,
+                                                 new_mean, new_var, part);
+    return bn_stats_launch<1, FoldAscending>(s, z, N * L, Rows{1}, ch, desc->bn_eps, momentum, gamma, beta, run_mean, run_var, stat, new_mean,
+                                             new_var, part);
 }
 
 // a = leaky(z s + t) into the GAP layout with zeroed gap rows (channels = 128) or y = z s + t flat (channels = 1)
@@ -644,15 +494,9 @@ extern "C" int stof_sincnet_train_apply(const float* z, int64_t N, int64_t L, in
     const int rc = dims_ok(N, L);
     if (rc != STOF_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const long long total = N * L * channels;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (channels == C) {
-        if (zero_gaps(s, out, N, L) != STOF_OK) return STOF_ERR_HIP;
-        hipLaunchKernelGGL(sn_apply_kernel<C>, grid, dim3(256), 0, s, z, total, (int)L, stat, out);
-    } else {
-        hipLaunchKernelGGL(sn_apply_kernel<1>, grid, dim3(256), 0, s, z, total, (int)L, stat, out);
-    }
-    return launched();
+    if (channels == 1) return bn_apply_launch<1, SincAct<false>>(s, z, N * L, Rows{1}, stat, out);
+    if (zero_gaps(s, out, N, L) != STOF_OK) return STOF_ERR_HIP;
+    return bn_apply_launch<4, SincAct<true>>(s, z, N * L, GapRows{(int)L}, stat, out);
 }
 
 // BatchNorm + LeakyReLU backward of one layer: da (the gradient of a; channels = 1: dy), a (NULL for channels = 1), z, stat of
@@ -668,11 +512,12 @@ extern "C" int stof_sincnet_train_bn_bwd(const float* da, const float* a, const 
     if (workspace_bytes < stof_sincnet_train_stats_workspace_bytes()) return STOF_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
-    if (channels == C) {
-        if (zero_gaps(s, dz, N, L) != STOF_OK) return STOF_ERR_HIP;
-        return bnb_launch<C>(s, da, a, z, stat, gamma, (int)(N * L), (int)L, dgamma, dbeta, dz, part);
-    }
-    return bnb_launch<1>(s, da, nullptr, z, stat, gamma, (int)(N * L), (int)L, dgamma, dbeta, dz, part);
+    double* coef = part + (size_t)ST_MAX_COPIES * 2 * channels;
+    const Chunks ch = balanced_chunks(N * L, ST_CHUNK, ST_MAX_COPIES, 1);
+    if (channels == 1)
+        return bn_bnb_launch<1, 1, FoldAscending, SincAct<false>>(s, da, nullptr, z, stat, gamma, N * L, Rows{1}, ch, dgamma, dbeta, dz, part, coef);
+    if (zero_gaps(s, dz, N, L) != STOF_OK) return STOF_ERR_HIP;
+    return bn_bnb_launch<4, C, FoldAscending, SincAct<true>>(s, da, a, z, stat, gamma, N * L, GapRows{(int)L}, ch, dgamma, dbeta, dz, part, coef);
 }
 
 extern "C" size_t stof_sincnet_train_conv_wgrad_workspace_bytes(int32_t layer) {
@@ -690,14 +535,14 @@ extern "C" int stof_sincnet_train_conv_wgrad(int32_t layer, const float* a_prev,
     if (workspace_bytes < stof_sincnet_train_conv_wgrad_workspace_bytes(layer)) return STOF_ERR_WORKSPACE;
     const int KT = layer == 1 ? K1 : K2, K = KT * C, E = C * K + C;
     const int M = (int)(N * L);
-    const Chunks ch = chunks_of(M, SW_CHUNK, SW_MAX_COPIES);
+    const Chunks ch = balanced_chunks(M, SW_CHUNK, SW_MAX_COPIES, 1);
     float* copies = static_cast<float*>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)ch.copies, (unsigned)KT, 4);
-    if (layer == 1) hipLaunchKernelGGL(sn_wgrad_kernel<K1>, grid, dim3(256), 0, s, a_prev, dz, M, (int)L, ch.per, copies, E);
-    else hipLaunchKernelGGL(sn_wgrad_kernel<K2>, grid, dim3(256), 0, s, a_prev, dz, M, (int)L, ch.per, copies, E);
+    const dim3 grid((unsigned)ch.n, (unsigned)KT, 4);
+    if (layer == 1) hipLaunchKernelGGL(sn_wgrad_kernel<K1>, grid, dim3(256), 0, s, a_prev, dz, M, (int)L, (int)ch.per, copies, E);
+    else hipLaunchKernelGGL(sn_wgrad_kernel<K2>, grid, dim3(256), 0, s, a_prev, dz, M, (int)L, (int)ch.per, copies, E);
     if (launched() != STOF_OK) return STOF_ERR_HIP;
-    partial_reduce(s, copies, ch.copies, E, E, ConvTapsThenBias{dw, db, C, C, C, K, KT}, 1.f);
+    partial_reduce(s, copies, ch.n, E, E, ConvTapsThenBias{dw, db, C, C, C, K, KT}, 1.f);
     return launched();
 }
 
@@ -710,12 +555,12 @@ extern "C" int stof_sincnet_train_out_wgrad(const float* a2, const float* dz3, i
     if (rc != STOF_OK) return rc;
     if (workspace_bytes < stof_sincnet_train_out_wgrad_workspace_bytes()) return STOF_ERR_WORKSPACE;
     const int E = C * K3 + 1, M = (int)(N * L);
-    const Chunks ch = chunks_of(M, OW_CHUNK, OW_MAX_COPIES);
+    const Chunks ch = balanced_chunks(M, OW_CHUNK, OW_MAX_COPIES, 1);
     float* copies = static_cast<float*>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(sn_out_wgrad_kernel, dim3((unsigned)ch.copies), dim3(256), 0, s, a2, dz3, M, (int)L, ch.per, copies, E);
+    hipLaunchKernelGGL(sn_out_wgrad_kernel, dim3((unsigned)ch.n), dim3(256), 0, s, a2, dz3, M, (int)L, (int)ch.per, copies, E);
     if (launched() != STOF_OK) return STOF_ERR_HIP;
-    partial_reduce(s, copies, ch.copies, E, E, DwThenDb{dw, db, C * K3}, 1.f);
+    partial_reduce(s, copies, ch.n, E, E, DwThenDb{dw, db, C * K3}, 1.f);
     return launched();
 }
 
@@ -741,13 +586,13 @@ extern "C" int stof_sincnet_train_bank_grad(const float* x, const float* dz0, in
     if (rc != STOF_OK) return rc;
     if (workspace_bytes < stof_sincnet_train_bank_grad_workspace_bytes()) return STOF_ERR_WORKSPACE;
     const int64_t tblocks = (L + TILE0 - 1) / TILE0, tiles = N * tblocks;
-    const Chunks ch = chunks_of(tiles, 1, BG_MAX_COPIES);
+    const Chunks ch = balanced_chunks(tiles, 1, BG_MAX_COPIES, 1);
     float* copies = static_cast<float*>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(sn_bank_grad_kernel, dim3((unsigned)ch.copies, 8, 4), dim3(256), 0, s, x, dz0, (long long)L, (long long)tblocks,
-                       (long long)tiles, ch.per, copies);
+    hipLaunchKernelGGL(sn_bank_grad_kernel, dim3((unsigned)ch.n, 8, 4), dim3(256), 0, s, x, dz0, (long long)L, (long long)tblocks,
+                       (long long)tiles, (int)ch.per, copies);
     if (launched() != STOF_OK) return STOF_ERR_HIP;
-    partial_reduce(s, copies, ch.copies, C * K0P, C * K0P, BankTaps{G, K0, K0P}, 1.f);      // the packed tap 1023 is dropped
+    partial_reduce(s, copies, ch.n, C * K0P, C * K0P, BankTaps{G, K0, K0P}, 1.f);      // the packed tap 1023 is dropped
     return launched();
 }
 

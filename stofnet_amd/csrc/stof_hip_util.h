@@ -7,6 +7,9 @@
 
 namespace stof {
 
+// after a kernel launch: did the runtime take it?
+inline int launched() { return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP; }
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device setting, so a process that drives several GPUs
 // has to make it on each of them.  One instance per kernel: a bit per device ordinal, set after a successful call.
 // Relaxed atomics are enough -- losing a race only repeats an idempotent runtime call -- and this is the only state

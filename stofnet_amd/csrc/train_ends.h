@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "stof_common.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
@@ -184,7 +185,6 @@ __device__ inline void ends_in_dgrad(const float* __restrict__ g, const float* _
 // -------------------------------------------------------------------------------------------------------- host glue
 // N L within the range of the 32-bit indices (N, L >= 1)
 inline bool rows_ok(int64_t N, int64_t L) { return N <= MAX_ROWS / L; }
-inline int launched() { return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP; }
 // partials (work-groups) of a weight-gradient launch: one per chunk, `max_copies` at the most
 inline int wgrad_copies(int64_t rows, int chunk, int max_copies) {
     const int64_t chunks = (rows + chunk - 1) / chunk;

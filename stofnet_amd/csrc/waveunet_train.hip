@@ -8,16 +8,13 @@
 //   wt_pack_frag_kernel     the raw weight [cout][cin][taps] -> the B fragment image of wu_conv_kernel (flip = 0), or the
 //                           image of the data gradient W'[ci][co][d] = W[co][ci][taps - 1 - d] (flip = 1)
 //   wu_in_kernel<false>     encoder 0: z = conv(x) + bias            wu_conv_kernel<.., false>   every other conv: z
-//   wt_stats_partial/final  per channel sum z and sum z^2 in double from the first addition, one partial per row chunk, the
-//                           partials added in ascending order; mean, biased variance, rstd, s = gamma rstd, t = beta - mean s
-//                           and the new running statistics (unbiased by m / (m - 1)) in double
-//   wt_apply_kernel         a = leaky_0.1(z s + t) in double, rounded once.  The LeakyReLU decision of the backward is a > 0.
+//   bn_train.h              the train-mode BatchNorm with WaveAct below: the batch statistics and a = leaky_0.1(z s + t) in
+//                           double, rounded once.  The LeakyReLU decision of the backward is a > 0.
 //   wu_head_kernel          y = tanh(w[0:16] . o + w[16] x + b)
 // Backward:
 //   wt_head_bwd_kernel      dl = dy (1 - y^2); do = w[0:16] dl; the w[16] dl term of dx (only if dx is wanted)
 //   wt_head_wgrad_kernel    sum dl o, sum dl x, sum dl as row-chunk partials -> partial_reduce
-//   wt_bnb_partial/final    g = da (a > 0 ? 1 : 0.1), xh = (z - mean) rstd: sum g, sum g xh in double -> dbeta, dgamma
-//   wt_dz_kernel            dz = s (g - mean(g) - xh mean(g xh)) in double, rounded once
+//   bn_train.h              g = da (a > 0 ? 1 : 0.1) in double -> dbeta, dgamma, dz
 //   wt_wgrad_kernel         dW[co][ci][d] = sum_rows dz[row][co] in[row + d - pad][ci], fp32 MFMA with K over rows: a work-group
 //                           owns 16 output x 16 input channels and all taps (wave w: taps w, w + 4, ..) of one chunk of
 //                           (waveform, 64-position tile) units; `in` is the forward's virtual input, built in LDS by the
@@ -31,7 +28,7 @@
 //                           at even positions, written once
 //   wt_in_dgrad_kernel      encoder 0's data gradient (16 -> 1, 15 taps) + the head's term -> dx
 //
-// Bounded chunks (rows per partial at the least / partials at the most; beyond that the rows per partial grow):
+// Bounded chunks, cut by fill_chunks of wgrad_reduce.h (rows per partial at the least / partials at the most; beyond that the rows per partial grow):
 //   statistics, BN backward  ST_ROWS = 256 rows / ST_MAX = 256        head weights   HB_ROWS = 256 rows / HB_MAX = 256
 //   encoder-0 weights        IW_ROWS = 256 rows / IW_MAX = 256
 //   conv weights             whole 64-position tiles of one waveform (a tile past the end of a waveform is partly empty),
@@ -40,6 +37,7 @@
 #include <math.h>
 #include "stof_common.h"
 #include "waveunet_net.h"
+#include "bn_train.h"
 #include "wgrad_reduce.h"
 
 namespace {
@@ -50,17 +48,9 @@ constexpr int IW_ROWS = 256, IW_MAX = 256;
 constexpr int WG_TILES = 1, WG_MAX = 128;
 constexpr int MAX_C = 2 * CI * MAX_LAYERS;          // 384: the widest virtual input (decoder 0 of n = 12)
 
-struct Chunks { long long per; int n; };
-Chunks chunks_of(long long units, int min_per, int max_n) {
-    long long per = (units + max_n - 1) / max_n;
-    if (per < min_per) per = min_per;
-    return {per, (int)((units + per - 1) / per)};
-}
-
 bool rows_ok(int64_t N, int64_t L) { return N >= 1 && L >= 1 && L < (1ll << 31) && N < (1ll << 31) && N * L < (1ll << 31) - 64; }
 bool nrows_ok(int64_t rows) { return rows >= 1 && rows < (1ll << 31) - 64; }
 bool chan_ok(int c) { return c >= 16 && c <= MAX_C && c % 16 == 0; }
-int launched() { return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP; }
 
 // ------------------------------------------------------------------------------------------------------------ packing
 // image element (nt, g, lane, e) <- W[16 nt + (lane & 15)][channel][tap] of the image's own (Cin, Cout), see waveunet.hip
@@ -90,129 +80,16 @@ __global__ __launch_bounds__(256) void wt_pack_in_kernel(const float* __restrict
     out[threadIdx.x] = j < ENC_TAPS ? w[c * ENC_TAPS + j] : b[c];
 }
 
-// --------------------------------------------------------------------------------------------------------- statistics
-// grid (chunk, 64 channels); thread (cl = tid & 63, rl = tid >> 6) sums rows r0 + rl, r0 + rl + 4, .. of its channel; the four
-// row lanes fold as (0 + 1) + (2 + 3).  part [chunk][2][C].
-__global__ __launch_bounds__(256) void wt_stats_partial_kernel(const float* __restrict__ z, long long R, int C, long long rows_per,
-                                                               double* __restrict__ part) {
-    __shared__ double red[2][4][64];
-    const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6, c = 64 * blockIdx.y + cl;
-    const long long r0 = blockIdx.x * rows_per, r1 = r0 + rows_per < R ? r0 + rows_per : R;
-    double s = 0.0, ss = 0.0;
-    if (c < C)
-        for (long long r = r0 + rl; r < r1; r += 4) {
-            const double v = (double)z[r * C + c];
-            s += v;
-            ss += v * v;
-        }
-    red[0][rl][cl] = s;
-    red[1][rl][cl] = ss;
-    __syncthreads();
-    if (rl != 0 || c >= C) return;
-    part[((long long)blockIdx.x * 2 + 0) * C + c] = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
-    part[((long long)blockIdx.x * 2 + 1) * C + c] = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
-}
-
-// thread c: the partials in ascending order.  stat [4][C]: mean, rstd, s, t.
-__global__ __launch_bounds__(64) void wt_stats_final_kernel(const double* __restrict__ part, int copies, int C, long long R, double eps,
-                                                            double momentum, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, const float* __restrict__ run_mean,
-                                                            const float* __restrict__ run_var, double* __restrict__ stat,
-                                                            float* __restrict__ new_mean, float* __restrict__ new_var) {
-    const int c = blockIdx.x * 64 + threadIdx.x;
-    if (c >= C) return;
-    double s = 0.0, ss = 0.0;
-    for (int k = 0; k < copies; ++k) {
-        s += part[((long long)k * 2 + 0) * C + c];
-        ss += part[((long long)k * 2 + 1) * C + c];
-    }
-    const double m = (double)R, mean = s / m;
-    double var = ss / m - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + eps), sc = (double)gamma[c] * rstd;
-    stat[c] = mean;
-    stat[C + c] = rstd;
-    stat[2 * C + c] = sc;
-    stat[3 * C + c] = (double)beta[c] - mean * sc;
-    new_mean[c] = (float)((1.0 - momentum) * (double)run_mean[c] + momentum * mean);
-    new_var[c] = (float)((1.0 - momentum) * (double)run_var[c] + momentum * (var * m / (m - 1.0)));
-}
-
-// thread: four channels of one row
-__global__ __launch_bounds__(256) void wt_apply_kernel(const float* __restrict__ z, long long total4, int C, const double* __restrict__ stat,
-                                                       float* __restrict__ a) {
-    const long long at = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (at >= total4) return;
-    const int c = (int)((at * 4) % C);
-    const float4 v = *reinterpret_cast<const float4*>(z + at * 4);
-    const float in[4] = {v.x, v.y, v.z, v.w};
-    float o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double u = (double)in[k] * stat[2 * C + c + k] + stat[3 * C + c + k];
-        o[k] = (float)(u > 0.0 ? u : 0.1 * u);
-    }
-    *reinterpret_cast<float4*>(a + at * 4) = make_float4(o[0], o[1], o[2], o[3]);
-}
-
-// -------------------------------------------------------------------------------------------------- BatchNorm backward
-__global__ __launch_bounds__(256) void wt_bnb_partial_kernel(const float* __restrict__ da, const float* __restrict__ a,
-                                                             const float* __restrict__ z, const double* __restrict__ stat, long long R,
-                                                             int C, long long rows_per, double* __restrict__ part) {
-    __shared__ double red[2][4][64];
-    const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6, c = 64 * blockIdx.y + cl;
-    const long long r0 = blockIdx.x * rows_per, r1 = r0 + rows_per < R ? r0 + rows_per : R;
-    double s = 0.0, ss = 0.0;
-    if (c < C) {
-        const double mean = stat[c], rstd = stat[C + c];
-        for (long long r = r0 + rl; r < r1; r += 4) {
-            const double g = (double)da[r * C + c] * (a[r * C + c] > 0.f ? 1.0 : 0.1);
-            s += g;
-            ss += g * (((double)z[r * C + c] - mean) * rstd);
-        }
-    }
-    red[0][rl][cl] = s;
-    red[1][rl][cl] = ss;
-    __syncthreads();
-    if (rl != 0 || c >= C) return;
-    part[((long long)blockIdx.x * 2 + 0) * C + c] = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
-    part[((long long)blockIdx.x * 2 + 1) * C + c] = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
-}
-
-// coef [2][C]: mean(g), mean(g xh)
-__global__ __launch_bounds__(64) void wt_bnb_final_kernel(const double* __restrict__ part, int copies, int C, long long R,
-                                                          float* __restrict__ dgamma, float* __restrict__ dbeta, double* __restrict__ coef) {
-    const int c = blockIdx.x * 64 + threadIdx.x;
-    if (c >= C) return;
-    double s = 0.0, ss = 0.0;
-    for (int k = 0; k < copies; ++k) {
-        s += part[((long long)k * 2 + 0) * C + c];
-        ss += part[((long long)k * 2 + 1) * C + c];
-    }
-    dbeta[c] = (float)s;
-    dgamma[c] = (float)ss;
-    coef[c] = s / (double)R;
-    coef[C + c] = ss / (double)R;
-}
-
-__global__ __launch_bounds__(256) void wt_dz_kernel(const float* __restrict__ da, const float* __restrict__ a, const float* __restrict__ z,
-                                                    const double* __restrict__ stat, const double* __restrict__ coef, long long total4, int C,
-                                                    float* __restrict__ dz) {
-    const long long at = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (at >= total4) return;
-    const int c = (int)((at * 4) % C);
-    const float4 dav = *reinterpret_cast<const float4*>(da + at * 4), av = *reinterpret_cast<const float4*>(a + at * 4),
-                 zv = *reinterpret_cast<const float4*>(z + at * 4);
-    const float d4[4] = {dav.x, dav.y, dav.z, dav.w}, a4[4] = {av.x, av.y, av.z, av.w}, z4[4] = {zv.x, zv.y, zv.z, zv.w};
-    float o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double g = (double)d4[k] * (a4[k] > 0.f ? 1.0 : 0.1);
-        const double xh = ((double)z4[k] - stat[c + k]) * stat[C + c + k];
-        o[k] = (float)(stat[2 * C + c + k] * (g - coef[c + k] - xh * coef[C + c + k]));
-    }
-    *reinterpret_cast<float4*>(dz + at * 4) = make_float4(o[0], o[1], o[2], o[3]);
-}
+// ----------------------------------------------------------------------------------------------------------- BatchNorm
+// What Wave-U-Net brings to bn_train.h: dense [rows][C] tensors (Rows), 64 channels per work-group with four row parts folded
+// in pairs, the rows cut by the fill-to-minimum rule, and the slope, xhat and the LeakyReLU all in double.
+struct WaveAct {
+    static constexpr bool reads_a = true;
+    __device__ static double g(float da, float a) { return (double)da * (a > 0.f ? 1.0 : 0.1); }
+    __device__ static double seen(double xh) { return xh; }
+    __device__ static double scale(const float*, const double* stat, int C, int c) { return stat[2 * C + c]; }
+    __device__ static float out(double u) { return (float)(u > 0.0 ? u : 0.1 * u); }
+};
 
 // ---------------------------------------------------------------------------------------------------------------- head
 __global__ __launch_bounds__(256) void wt_head_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ w,
@@ -486,21 +363,15 @@ extern "C" int stof_waveunet_train_stats(const float* z, int64_t rows, int32_t c
     if (!nrows_ok(rows) || rows < 2 || !chan_ok(ch) || !z || !gamma || !beta || !run_mean || !run_var || !stat || !new_mean || !new_var)
         return STOF_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < stof_waveunet_train_stats_workspace_bytes()) return STOF_ERR_WORKSPACE;
-    const Chunks cs = chunks_of(rows, ST_ROWS, ST_MAX);
+    const Chunks cs = fill_chunks(rows, ST_ROWS, ST_MAX);
     double* part = static_cast<double*>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(wt_stats_partial_kernel, dim3(cs.n, (ch + 63) / 64), dim3(256), 0, s, z, (long long)rows, ch, cs.per, part);
-    hipLaunchKernelGGL(wt_stats_final_kernel, dim3((ch + 63) / 64), dim3(64), 0, s, part, cs.n, ch, (long long)rows, eps, momentum, gamma, beta,
-                       run_mean, run_var, stat, new_mean, new_var);
-    return launched();
+    return bn_stats_launch<64, FoldPairs>(s, z, rows, Rows{ch}, cs, eps, momentum, gamma, beta, run_mean, run_var, stat, new_mean, new_var, part);
 }
 
 extern "C" int stof_waveunet_train_apply(const float* z, int64_t rows, int32_t ch, const double* stat, float* a, void* stream) {
     if (!nrows_ok(rows) || !chan_ok(ch) || !z || !stat || !a) return STOF_ERR_BAD_ARG;
-    const long long total4 = rows * ch / 4;
-    hipLaunchKernelGGL(wt_apply_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), z, total4, ch,
-                       stat, a);
-    return launched();
+    return bn_apply_launch<4, WaveAct>(static_cast<hipStream_t>(stream), z, rows, Rows{ch}, stat, a);
 }
 
 extern "C" int stof_waveunet_train_head(const float* o, const float* x, int64_t N, int64_t L, const float* w, const float* b, float* y,
@@ -522,7 +393,7 @@ extern "C" int stof_waveunet_train_head_bwd(const float* dy, const float* y, con
     const long long M = N * L;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(wt_head_bwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, dy, y, w, M, dout, dxh);
-    const Chunks cs = chunks_of(M, HB_ROWS, HB_MAX);
+    const Chunks cs = fill_chunks(M, HB_ROWS, HB_MAX);
     float* part = static_cast<float*>(workspace);
     hipLaunchKernelGGL(wt_head_wgrad_kernel, dim3(cs.n), dim3(256), 0, s, dy, y, o, x, M, cs.per, part);
     partial_reduce(s, part, cs.n, CI + 2, CI + 2, DwThenDb{dw, db, CI + 1}, 1.f);
@@ -533,20 +404,16 @@ extern "C" int stof_waveunet_train_bn_bwd(const float* da, const float* a, const
                                           float* dgamma, float* dbeta, float* dz, void* workspace, size_t workspace_bytes, void* stream) {
     if (!nrows_ok(rows) || rows < 2 || !chan_ok(ch) || !da || !a || !z || !stat || !dgamma || !dbeta || !dz) return STOF_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < stof_waveunet_train_stats_workspace_bytes()) return STOF_ERR_WORKSPACE;
-    const Chunks cs = chunks_of(rows, ST_ROWS, ST_MAX);
+    const Chunks cs = fill_chunks(rows, ST_ROWS, ST_MAX);
     double* part = static_cast<double*>(workspace);
     double* coef = part + (size_t)ST_MAX * 2 * MAX_C;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(wt_bnb_partial_kernel, dim3(cs.n, (ch + 63) / 64), dim3(256), 0, s, da, a, z, stat, (long long)rows, ch, cs.per, part);
-    hipLaunchKernelGGL(wt_bnb_final_kernel, dim3((ch + 63) / 64), dim3(64), 0, s, part, cs.n, ch, (long long)rows, dgamma, dbeta, coef);
-    const long long total4 = rows * ch / 4;
-    hipLaunchKernelGGL(wt_dz_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, da, a, z, stat, coef, total4, ch, dz);
-    return launched();
+    return bn_bnb_launch<4, 64, FoldPairs, WaveAct>(s, da, a, z, stat, nullptr, rows, Rows{ch}, cs, dgamma, dbeta, dz, part, coef);
 }
 
 extern "C" size_t stof_waveunet_train_wgrad_workspace_bytes(int64_t N, int64_t Lout, int32_t cin, int32_t cout, int32_t taps) {
     if (!rows_ok(N, Lout) || !chan_ok(cin) || !chan_ok(cout) || (taps != ENC_TAPS && taps != DEC_TAPS)) return 0;
-    const Chunks cs = chunks_of(N * ((Lout + TM - 1) / TM), WG_TILES, WG_MAX);
+    const Chunks cs = fill_chunks(N * ((Lout + TM - 1) / TM), WG_TILES, WG_MAX);
     return (size_t)cs.n * ((size_t)cout * taps * cin + cout) * sizeof(float);
 }
 
@@ -563,7 +430,7 @@ extern "C" int stof_waveunet_train_wgrad(const float* src, const float* low, con
     w.dz = dz;
     w.part = static_cast<float*>(workspace);
     w.units = N * w.c.tiles;
-    const Chunks cs = chunks_of(w.units, WG_TILES, WG_MAX);
+    const Chunks cs = fill_chunks(w.units, WG_TILES, WG_MAX);
     w.units_per = cs.per;
     w.E = (long long)cout * taps * cin + cout;
     if (w.E >= (1ll << 31)) return STOF_ERR_UNSUPPORTED;
@@ -584,7 +451,7 @@ extern "C" int stof_waveunet_train_in_wgrad(const float* x, const float* dz, int
     if (!rows_ok(N, L) || !x || !dz || !dw || !db) return STOF_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < stof_waveunet_train_in_wgrad_workspace_bytes()) return STOF_ERR_WORKSPACE;
     const long long M = N * L;
-    const Chunks cs = chunks_of(M, IW_ROWS, IW_MAX);
+    const Chunks cs = fill_chunks(M, IW_ROWS, IW_MAX);
     float* part = static_cast<float*>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(wt_in_wgrad_kernel, dim3(cs.n), dim3(256), 0, s, x, dz, M, (long long)L, cs.per, part);

@@ -8,10 +8,41 @@
 //
 // Where the sum of element i goes is the caller's `Map`: used(i) (false: a slot that no partial holds) and store(i, value).
 // (wgrad_reduce_kernel and sgb_wgrad_reduce_kernel of train.hip are a different scheme.)
+//
+// Also here, because it decides what a partial holds: how the rows (or tiles) of a reduction are cut into the chunks that one
+// work-group each sums.  The rule fixes the order of every fixed-order sum behind it, so it is part of the results' bits: a
+// kernel keeps the rule it was written with (tests/test_gpu_baseline_train_bits.py and test_gpu_train_ends_bits.py pin them).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "stof_hip_util.h"
 
 namespace {
+
+using stof::launched;
+
+// n chunks of `per` units each, the last one possibly shorter
+struct Chunks {
+    long long per;
+    int n;
+};
+
+// Balanced: as many chunks as `min_per` units each would make, `max_n` at the most, then the units spread evenly over them and
+// `per` rounded up to a multiple of `multiple` (Zonzini: 2, an MFMA row pair never straddles two chunks; SincNet: 1).
+inline Chunks balanced_chunks(int64_t units, int min_per, int max_n, int multiple) {
+    int64_t c = (units + min_per - 1) / min_per;
+    if (c > max_n) c = max_n;
+    int64_t per = (units + c - 1) / c;
+    per = (per + multiple - 1) / multiple * multiple;
+    return {per, (int)((units + per - 1) / per)};
+}
+
+// Fill to the minimum (Wave-U-Net): every chunk holds `min_per` units until `max_n` chunks are not enough, then they grow.
+inline Chunks fill_chunks(int64_t units, int min_per, int max_n) {
+    int64_t per = (units + max_n - 1) / max_n;
+    if (per < min_per) per = min_per;
+    return {per, (int)((units + per - 1) / per)};
+}
 
 // elements 0 .. ndw - 1 are dw, the rest db
 struct DwThenDb {

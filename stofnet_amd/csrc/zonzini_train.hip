@@ -4,7 +4,8 @@
 //
 //   forward               the kernels of zonzini_net.h with TRAIN = true: every pooled activation and its selectors are kept,
 //                         the head also saves f [N][C] and h [N][1024] (post-ReLU).  y is bitwise the inference y.
-//   zz_pack_*_kernel      the forward kernels' blob packed on the device from the parameters (bytes of the host packer)
+//   zz_copy / zz_pack_fc1t_kernel, pack_frag32_kernel (mfma32_frag.h)
+//                         the forward kernels' blob packed on the device from the parameters (bytes of the host packer)
 //   zz_head_units_kernel  dfc2.weight, dfc2.bias, dfc1.bias: thread = fc1 unit, one chain over n = 0 .. N - 1
 //   zz_head_w1_kernel     dfc1.weight [1024][C]: thread = element, one chain over n = 0 .. N - 1
 //   zz_head_df_kernel     df [N][cpad] = dh W1 (pad 0), dh = dy w2 [h > 0]: four interleaved chains over the units (j mod 4),
@@ -58,18 +59,6 @@ int shape_of(const stof_zonzini_desc* desc, int64_t N, int64_t L, Shape& s) {
     return STOF_OK;
 }
 
-inline int launched() { return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP; }
-
-// chunking of M rows: `copies` chunks of `rows_per` rows (even, so that an MFMA row pair never straddles two chunks)
-struct Chunks { int copies, rows_per; };
-inline Chunks chunks_of(int64_t M, int chunk, int max_copies) {
-    int64_t c = (M + chunk - 1) / chunk;
-    if (c > max_copies) c = max_copies;
-    int64_t per = (M + c - 1) / c;
-    per += per & 1;
-    return {(int)((M + per - 1) / per), (int)per};
-}
-
 inline int64_t wgrad_e(const Geometry& g, int l) { return (int64_t)g.cout[l] * (KW * g.cpad[l - 1] + 1); }     // dW [co][k], then db
 inline int wgrad_max_copies(const Geometry& g, int l) {
     const int64_t fit = (int64_t)(ZW_WORKSPACE / sizeof(float)) / wgrad_e(g, l);
@@ -92,18 +81,6 @@ struct Grad {
 __global__ __launch_bounds__(256) void zz_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int n) {
     const int o = blockIdx.x * 256 + threadIdx.x;
     if (o < n) dst[o] = src[o];
-}
-
-// pack_frag32 of mfma32_frag.h for a conv weight (cout, cin, 10) with k = tap * cin_pad + ci
-__global__ __launch_bounds__(256) void zz_pack_frag_kernel(const float* __restrict__ w, int cout, int cin, int cin_pad, int groups,
-                                                           float* __restrict__ out, int total) {
-    const int o = blockIdx.x * 256 + threadIdx.x;
-    if (o >= total) return;
-    const int e = o & 3, lane = (o >> 2) & 63, rest = o >> 8;
-    const int q = rest % groups, nt = rest / groups;
-    const int oc = 32 * nt + (lane & 31), k = 8 * q + 4 * (lane >> 5) + e;
-    const int tap = k / cin_pad, ci = k - tap * cin_pad;
-    out[o] = (oc < cout && ci < cin && tap < KW) ? w[((size_t)oc * cin + ci) * KW + tap] : 0.f;
 }
 
 // fc1.weight [1024][C] -> fc1t [C][1024]
@@ -235,12 +212,9 @@ __global__ __launch_bounds__(256) void zz_dgrad_image_kernel(const float* __rest
                                                              int groups, float* __restrict__ out, int total) {
     const int o = blockIdx.x * 256 + threadIdx.x;
     if (o >= total) return;
-    const int e = o & 3, lane = (o >> 2) & 63;
-    int rest = o >> 8;
-    const int q = rest % groups;
-    rest /= groups;
-    const int nt = rest % nt_in, parity = rest / nt_in;
-    const int ci = 32 * nt + (lane & 31), k = 8 * q + 4 * (lane >> 5) + e;
+    int tile, row, k;                                                 // tile = parity * nt_in + ci tile
+    frag_decode(o, groups, tile, row, k);
+    const int parity = tile / nt_in, ci = row - 32 * parity * nt_in;
     const int jj = k / cpad_out, co = k - jj * cpad_out;
     out[o] = (jj < 5 && co < cout && ci < cin) ? w[((size_t)co * cin + ci) * KW + 2 * jj + parity] : 0.f;
 }
@@ -410,8 +384,7 @@ extern "C" int stof_zonzini_train_pack(const stof_zonzini_desc* desc, const floa
     copy(params[1], o.c1b, g.cout[0]);
     for (int l = 1; l < g.layers; ++l) {
         const int groups = KW * g.cpad[l - 1] / 8, total = ntiles(g.cout[l]) * groups * 256;
-        hipLaunchKernelGGL(zz_pack_frag_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, params[2 * l], g.cout[l],
-                           g.cout[l - 1], g.cpad[l - 1], groups, blob + o.frag[l], total);
+        pack_frag32_device(s, params[2 * l], g.cout[l], g.cout[l - 1], KW, g.cpad[l - 1], groups, blob + o.frag[l], total);
         copy(params[2 * l + 1], o.bias[l], g.cout[l]);
     }
     const int C = g.cout[g.layers - 1];
@@ -493,15 +466,15 @@ extern "C" int stof_zonzini_train_conv_wgrad(const stof_zonzini_desc* desc, int3
     if (workspace_bytes < stof_zonzini_train_conv_wgrad_workspace_bytes(desc, layer)) return STOF_ERR_WORKSPACE;
     const int l = layer, K = KW * g.cpad[l - 1], E = (int)wgrad_e(g, l);
     const int64_t lp = sh.len[l + 1], M = N * lp;
-    const Chunks ch = chunks_of(M, ZW_CHUNK, wgrad_max_copies(g, l));
+    const Chunks ch = balanced_chunks(M, ZW_CHUNK, wgrad_max_copies(g, l), 2);
     float* copies = static_cast<float*>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int ktiles = (K + 31) / 32;
-    const dim3 grid((unsigned)ch.copies, (unsigned)((ktiles + 3) / 4), (unsigned)ntiles(g.cout[l]));
+    const dim3 grid((unsigned)ch.n, (unsigned)((ktiles + 3) / 4), (unsigned)ntiles(g.cout[l]));
     hipLaunchKernelGGL(zz_wgrad_kernel, grid, dim3(256), 0, s, in, (int)sh.len[l], g.cpad[l - 1], grad_of(sh, l, dout), sel, (int)M,
-                       (int)lp, ch.rows_per, g.cout[l], g.cpad[l], K, copies, E);
+                       (int)lp, (int)ch.per, g.cout[l], g.cpad[l], K, copies, E);
     if (launched() != STOF_OK) return STOF_ERR_HIP;
-    partial_reduce(s, copies, ch.copies, E, E, ConvTapsThenBias{dw, db, g.cout[l], g.cout[l - 1], g.cpad[l - 1], K, KW}, 1.f);
+    partial_reduce(s, copies, ch.n, E, E, ConvTapsThenBias{dw, db, g.cout[l], g.cout[l - 1], g.cpad[l - 1], K, KW}, 1.f);
     return launched();
 }
 
@@ -554,14 +527,14 @@ extern "C" int stof_zonzini_train_in_wgrad(const stof_zonzini_desc* desc, const 
     const Geometry& g = sh.g;
     if (workspace_bytes < stof_zonzini_train_in_wgrad_workspace_bytes(desc)) return STOF_ERR_WORKSPACE;
     const int64_t lp = sh.len[1], M = N * lp;
-    const Chunks ch = chunks_of(M, ZW1_CHUNK, ZW1_MAX_COPIES);
+    const Chunks ch = balanced_chunks(M, ZW1_CHUNK, ZW1_MAX_COPIES, 2);
     const int E = g.cout[0] * (KW + 1);
     float* copies = static_cast<float*>(workspace);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(zz_in_wgrad_kernel, dim3((unsigned)ch.copies), dim3(256), 0, s, x, (int)L, dout, sel, (int)M, (int)lp, ch.rows_per,
+    hipLaunchKernelGGL(zz_in_wgrad_kernel, dim3((unsigned)ch.n), dim3(256), 0, s, x, (int)L, dout, sel, (int)M, (int)lp, (int)ch.per,
                        g.cout[0], g.cpad[0], copies, E);
     if (launched() != STOF_OK) return STOF_ERR_HIP;
-    partial_reduce(s, copies, ch.copies, E, E, DwThenDb{dw, db, g.cout[0] * KW}, 1.f);
+    partial_reduce(s, copies, ch.n, E, E, DwThenDb{dw, db, g.cout[0] * KW}, 1.f);
     return launched();
 }
 

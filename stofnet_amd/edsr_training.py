@@ -46,14 +46,13 @@ class EdsrTrainEngine(SavedStepEngine):
 
     def _forward_saved(self, p, frame):
         """models/edsr_1d.py:38-45 -> (y [N, L r], EdsrSaved)."""
-        lib, st = _lib.lib(), self._st()
+        st = self._st()
         x = self._flat_frame(frame)
         n, L = x.shape
         p = {k: v.contiguous() for k, v in p.items()}
         fwd = {nm: self._image(p, nm, False) for nm in self.body_layers()}
         a0 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_train_edsr_in(_lib.ptr(x), _lib.ptr(p['conv_input.weight']), _lib.ptr(p['conv_input.bias']), _lib.ptr(a0),
-                                          n, L, st), 'stof_train_edsr_in')
+        _lib.call('stof_train_edsr_in', x, p['conv_input.weight'], p['conv_input.bias'], a0, n, L, st)
         u, hs, us = a0, [], [a0]
         for i in range(self.B):
             c1, c2 = f'residual_blocks.{i}.conv1', f'residual_blocks.{i}.conv2'
@@ -63,24 +62,20 @@ class EdsrTrainEngine(SavedStepEngine):
             us.append(u)
         trunk = self._conv(u, fwd['conv_mid'], p['conv_mid.bias'], 64, 64, 3, ACT_NONE, residual=a0)
         y = torch.empty((n, L * self.r), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_train_edsr_out(_lib.ptr(trunk), _lib.ptr(p['conv_output.weight']), _lib.ptr(p['conv_output.bias']),
-                                           _lib.ptr(y), n, L, self.r, st), 'stof_train_edsr_out')
+        _lib.call('stof_train_edsr_out', trunk, p['conv_output.weight'], p['conv_output.bias'], y, n, L, self.r, st)
         return y, EdsrSaved(p=p, versions={k: v._version for k, v in p.items()}, x=x, a0=a0, hs=hs, us=us, trunk=trunk)
 
     def _backward_saved(self, saved, dy, g, dx=None):
         """From dy [N, L r] = dloss/dy: every parameter gradient into the tensors of `g` (name -> tensor of the parameter's
         shape) and, if `dx` [N, L] is given, the gradient with respect to the input frame into it."""
-        lib, st, p, r = _lib.lib(), self._st(), saved.p, self.r
+        st, p, r = self._st(), saved.p, self.r
         n, L = saved.x.shape
         self._check_versions(saved)
         bwd = {nm: self._image(p, nm, True) for nm in self.body_layers()}
-        ws = self._scratch('_edsr_out_ws', lib.stof_train_edsr_out_wgrad_workspace_bytes(r))
-        _lib.check(lib.stof_train_edsr_out_wgrad(_lib.ptr(saved.trunk), _lib.ptr(dy), _lib.ptr(g['conv_output.weight']),
-                                                 _lib.ptr(g['conv_output.bias']), n, L, r, 1.0, _lib.ptr(ws), ws.numel(), st),
-                   'stof_train_edsr_out_wgrad')
+        ws = self._scratch('_edsr_out_ws', _lib.call('stof_train_edsr_out_wgrad_workspace_bytes', r))
+        _lib.call('stof_train_edsr_out_wgrad', saved.trunk, dy, g['conv_output.weight'], g['conv_output.bias'], n, L, r, 1.0, ws, ws.numel(), st)
         gt = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)            # dloss/dtrunk: also the long skip's gradient
-        _lib.check(lib.stof_train_edsr_out_dgrad(_lib.ptr(dy), _lib.ptr(p['conv_output.weight']), _lib.ptr(gt), n, L, r, st),
-                   'stof_train_edsr_out_dgrad')
+        _lib.call('stof_train_edsr_out_dgrad', dy, p['conv_output.weight'], gt, n, L, r, st)
         self._wgrad(saved.us[self.B], gt, g['conv_mid.weight'], g['conv_mid.bias'], 64, 64, 3)
         gu = self._conv(gt, bwd['conv_mid'], None, 64, 64, 3)
         for i in range(self.B - 1, -1, -1):                  # gu = dloss/d(output of block i), the identity path included
@@ -89,13 +84,10 @@ class EdsrTrainEngine(SavedStepEngine):
             gh = self._conv(gu, bwd[c2], None, 64, 64, 3, ACT_RELU, saved=saved.hs[i])
             self._wgrad(saved.us[i], gh, g[c1 + '.weight'], g[c1 + '.bias'], 64, 64, 3)
             gu = self._conv(gh, bwd[c1], None, 64, 64, 3, residual=gu)
-        ws = self._scratch('_edsr_in_ws', lib.stof_train_edsr_in_wgrad_workspace_bytes())
-        _lib.check(lib.stof_train_edsr_in_wgrad(_lib.ptr(saved.x), _lib.ptr(gu), _lib.ptr(gt), _lib.ptr(saved.a0),
-                                                _lib.ptr(g['conv_input.weight']), _lib.ptr(g['conv_input.bias']), n, L, 1.0,
-                                                _lib.ptr(ws), ws.numel(), st), 'stof_train_edsr_in_wgrad')
+        ws = self._scratch('_edsr_in_ws', _lib.call('stof_train_edsr_in_wgrad_workspace_bytes'))
+        _lib.call('stof_train_edsr_in_wgrad', saved.x, gu, gt, saved.a0, g['conv_input.weight'], g['conv_input.bias'], n, L, 1.0, ws, ws.numel(), st)
         if dx is not None:
-            _lib.check(lib.stof_train_edsr_in_dgrad(_lib.ptr(gu), _lib.ptr(gt), _lib.ptr(saved.a0), _lib.ptr(p['conv_input.weight']),
-                                                    _lib.ptr(dx), n, L, 1.0, st), 'stof_train_edsr_in_dgrad')
+            _lib.call('stof_train_edsr_in_dgrad', gu, gt, saved.a0, p['conv_input.weight'], dx, n, L, 1.0, st)
 
 
 class EdsrFunction(EndsFunction):

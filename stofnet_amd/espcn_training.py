@@ -33,54 +33,44 @@ class EspcnTrainEngine(SavedStepEngine):
 
     def _repack_mid(self, w):
         """conv2.weight as the MFMA operand of `stof_train_espcn_mid`"""
-        lib = _lib.lib()
-        img = torch.empty(lib.stof_train_espcn_repack_floats(), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_train_espcn_repack(_lib.ptr(w), _lib.ptr(img), self._st()), 'stof_train_espcn_repack')
+        img = torch.empty(_lib.call('stof_train_espcn_repack_floats'), dtype=torch.float32, device=self.dev)
+        _lib.call('stof_train_espcn_repack', w, img, self._st())
         return img
 
     def _forward_saved(self, p, frame):
         """models/espcn_1d.py:31-36 -> (y [N, L r], EspcnSaved)."""
-        lib, st, r = _lib.lib(), self._st(), self.r
+        st, r = self._st(), self.r
         x = self._flat_frame(frame)
         n, L = x.shape
         p = {k: v.contiguous() for k, v in p.items()}
         h1 = torch.empty((n, L, 64), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_train_espcn_in(_lib.ptr(x), _lib.ptr(p['conv1.weight']), _lib.ptr(p['conv1.bias']), _lib.ptr(h1), n, L, st),
-                   'stof_train_espcn_in')
+        _lib.call('stof_train_espcn_in', x, p['conv1.weight'], p['conv1.bias'], h1, n, L, st)
         h2 = torch.empty((n, L, 32), dtype=torch.float32, device=self.dev)
         w2 = p['conv2.weight']
         mid = self._cached('mid', w2, lambda: self._repack_mid(w2))
-        _lib.check(lib.stof_train_espcn_mid(_lib.ptr(h1), _lib.ptr(mid), _lib.ptr(p['conv2.bias']), _lib.ptr(h2), n, L, st),
-                   'stof_train_espcn_mid')
+        _lib.call('stof_train_espcn_mid', h1, mid, p['conv2.bias'], h2, n, L, st)
         y = torch.empty((n, L * r), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_train_espcn_out(_lib.ptr(h2), _lib.ptr(p['conv3.weight']), _lib.ptr(p['conv3.bias']), _lib.ptr(y), n, L, r, st),
-                   'stof_train_espcn_out')
+        _lib.call('stof_train_espcn_out', h2, p['conv3.weight'], p['conv3.bias'], y, n, L, r, st)
         return y, EspcnSaved(p=p, versions={k: v._version for k, v in p.items()}, x=x, h1=h1, h2=h2, y=y)
 
     def _backward_saved(self, saved, dy, g, dx=None):
         """From dy [N, L r] = dloss/dy: every parameter gradient into the tensors of `g` (name -> tensor of the parameter's
         shape) and, if `dx` [N, L] is given, the gradient with respect to the input frame into it."""
-        lib, st, p, r = _lib.lib(), self._st(), saved.p, self.r
+        st, p, r = self._st(), saved.p, self.r
         n, L = saved.x.shape
         self._check_versions(saved)
-        ws = self._scratch('_espcn_out_ws', lib.stof_train_espcn_out_wgrad_workspace_bytes(r))
-        _lib.check(lib.stof_train_espcn_out_wgrad(_lib.ptr(saved.h2), _lib.ptr(saved.y), _lib.ptr(dy), _lib.ptr(g['conv3.weight']),
-                                                  _lib.ptr(g['conv3.bias']), n, L, r, 1.0, _lib.ptr(ws), ws.numel(), st),
-                   'stof_train_espcn_out_wgrad')
+        ws = self._scratch('_espcn_out_ws', _lib.call('stof_train_espcn_out_wgrad_workspace_bytes', r))
+        _lib.call('stof_train_espcn_out_wgrad', saved.h2, saved.y, dy, g['conv3.weight'], g['conv3.bias'], n, L, r, 1.0, ws, ws.numel(), st)
         g2 = torch.empty((n, L, 32), dtype=torch.float32, device=self.dev)            # dloss/d(conv2's output), tanh' included
-        _lib.check(lib.stof_train_espcn_out_dgrad(_lib.ptr(saved.y), _lib.ptr(dy), _lib.ptr(saved.h2), _lib.ptr(p['conv3.weight']),
-                                                  _lib.ptr(g2), n, L, r, st), 'stof_train_espcn_out_dgrad')
+        _lib.call('stof_train_espcn_out_dgrad', saved.y, dy, saved.h2, p['conv3.weight'], g2, n, L, r, st)
         self._wgrad(saved.h1, g2, g['conv2.weight'], g['conv2.bias'], 64, 32, 3)
         w2 = p['conv2.weight']
         flip = self._cached('flip', w2, lambda: self._repack(w2, True))               # the data-gradient operand of `stof_train_conv`
         g1 = self._conv(g2, flip, None, 32, 64, 3)                                    # dloss/dh1: tanh' of h1 is applied by its readers
-        ws = self._scratch('_espcn_in_ws', lib.stof_train_espcn_in_wgrad_workspace_bytes())
-        _lib.check(lib.stof_train_espcn_in_wgrad(_lib.ptr(saved.x), _lib.ptr(g1), _lib.ptr(saved.h1), _lib.ptr(g['conv1.weight']),
-                                                 _lib.ptr(g['conv1.bias']), n, L, 1.0, _lib.ptr(ws), ws.numel(), st),
-                   'stof_train_espcn_in_wgrad')
+        ws = self._scratch('_espcn_in_ws', _lib.call('stof_train_espcn_in_wgrad_workspace_bytes'))
+        _lib.call('stof_train_espcn_in_wgrad', saved.x, g1, saved.h1, g['conv1.weight'], g['conv1.bias'], n, L, 1.0, ws, ws.numel(), st)
         if dx is not None:
-            _lib.check(lib.stof_train_espcn_in_dgrad(_lib.ptr(g1), _lib.ptr(saved.h1), _lib.ptr(p['conv1.weight']), _lib.ptr(dx), n, L,
-                                                     1.0, st), 'stof_train_espcn_in_dgrad')
+            _lib.call('stof_train_espcn_in_dgrad', g1, saved.h1, p['conv1.weight'], dx, n, L, 1.0, st)
 
 
 class EspcnFunction(EndsFunction):

@@ -264,6 +264,7 @@ class SincNet(_PackedKernels, nn.Module):
         graph when one is recorded: its backward fills the gradient of all 16 parameters (and of x, if it asks for one) in
         exact fp32.  BatchNorm uses batch statistics and the running statistics are updated, also under no_grad.  Not chunked
         by `max_workspace_bytes`: the batch statistics and the backward need every activation of the whole batch."""
+        from ._train_boundary import commit_running_stats, fp32_device_params, train_engine
         from .sincnet_training import SincNetFunction, SincNetTrainEngine
         if not self.training:
             raise NotImplementedError("SincNet: train_route='kernels' serves train mode only; an eval-mode backward (running "
@@ -273,26 +274,14 @@ class SincNet(_PackedKernels, nn.Module):
             raise ValueError(f'Expected more than 1 value per channel when training, got input size {torch.Size([1, N_FILT, 1])}')
         self._check_frame(x)
         N, L = int(x.shape[0]), int(x.shape[-1])
-        names, params = zip(*self.named_parameters())
-        for p in params:
-            if p.dtype != torch.float32:
-                raise TypeError(f'SincNet: parameters must be float32 (got {p.dtype}); the gfx950 kernels are fp32 only')
-            _lib.require_device(p, 'parameter')
+        names, params = fp32_device_params(self, 'SincNet')
         desc = self._desc()
-        engines = self.__dict__.setdefault('_train_engines', {})
-        key = (str(x.device), desc.fs, desc.bn_eps)
-        if key not in engines:
-            engines[key] = SincNetTrainEngine(x.device, desc.fs, desc.bn_eps)
-        engine = engines[key]
+        engine = train_engine(self, (str(x.device), desc.fs, desc.bn_eps), lambda: SincNetTrainEngine(x.device, desc.fs, desc.bn_eps))
         engine.momentum = float(self.bn[0].momentum)
         engine.running = [(bn.running_mean, bn.running_var) for bn in self.bn]
         y = SincNetFunction.apply(x.reshape(N, 1, L), engine, names, *params)
         if N and L:
-            with torch.no_grad():                # on the host side: `copy_` bumps the buffers' versions (the eval-mode blob's key)
-                for bn, (mean, var) in zip(self.bn, engine.new_running):
-                    bn.running_mean.copy_(mean)
-                    bn.running_var.copy_(var)
-                    bn.num_batches_tracked.add_(1)
+            commit_running_stats(self.bn, engine.new_running)
         return y
 
     def forward(self, x):

@@ -58,9 +58,8 @@ class SincNetTrainEngine(SavedStepEngine):
         self.names = list(NAMES)
         self.running = None         # per layer (running_mean, running_var) to blend into; None: zeros and ones
         self.new_running = None     # per layer (new running_mean, new running_var) of the last forward
-        self._blob = None
         lay = (ctypes.c_int64 * 6)()
-        _lib.check(_lib.lib().stof_sincnet_train_blob_layout(lay), 'stof_sincnet_train_blob_layout')
+        _lib.call('stof_sincnet_train_blob_layout', lay)
         self.blob_layout = dict(zip(('frag0', 'bank_t', 'frag1', 'frag2', 'w3', 'total'), (int(v) for v in lay)))
 
     def _desc(self):
@@ -68,7 +67,7 @@ class SincNetTrainEngine(SavedStepEngine):
 
     def buffer(self, n, L):
         """an uninitialised 128-channel tensor in the GAP layout"""
-        return torch.empty(int(_lib.lib().stof_sincnet_train_buffer_floats(n, L)), dtype=torch.float32, device=self.dev)
+        return torch.empty(int(_lib.call('stof_sincnet_train_buffer_floats', n, L)), dtype=torch.float32, device=self.dev)
 
     def rows(self, buf, n, L):
         """the [N, L, 128] view of a GAP-layout buffer"""
@@ -82,101 +81,76 @@ class SincNetTrainEngine(SavedStepEngine):
         return buf
 
     def packed(self, p):
-        """The forward kernels' blob of this step's parameters, packed on the device again when one of them changed."""
-        version = tuple((p[k].data_ptr(), p[k]._version) for k in _PACKED)
-        if self._blob is None or self._blob[0] != version:
-            lib, desc = _lib.lib(), self._desc()
-            nbytes = 4 * self.blob_layout['total']
-            blob = self._blob[1] if self._blob is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-            ptrs = (ctypes.c_void_p * len(_PACKED))(*[p[k].data_ptr() for k in _PACKED])
-            _lib.check(lib.stof_sincnet_train_pack(ctypes.byref(desc), ptrs, _lib.ptr(blob), nbytes, self._st()),
-                       'stof_sincnet_train_pack')
-            self._blob = (version, blob)
-        return self._blob[1]
+        """The forward kernels' blob of this step's parameters."""
+        return self._packed_blob(p, _PACKED, 4 * self.blob_layout['total'], 'stof_sincnet_train_pack', self._desc())
 
     def _dgrad_image(self, layer, w):
         img = torch.empty(C * TAPS[layer] * C, dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().stof_sincnet_train_dgrad_image(layer, _lib.ptr(w), _lib.ptr(img), self._st()),
-                   'stof_sincnet_train_dgrad_image')
+        _lib.call('stof_sincnet_train_dgrad_image', layer, w, img, self._st())
         return img
 
     def _stats_ws(self):
-        return self._scratch('_sn_stats_ws', _lib.lib().stof_sincnet_train_stats_workspace_bytes())
+        return self._scratch('_sn_stats_ws', _lib.call('stof_sincnet_train_stats_workspace_bytes'))
 
     # -------------------------------------------------------------------------------------------- one kernel stage each
     def conv(self, layer, src, n, L, blob, bias):
         out = self.buffer(n, L) if layer < 3 else torch.empty(n * L, dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().stof_sincnet_train_conv(layer, _lib.ptr(src), n, L, _lib.ptr(blob), _lib.ptr(bias), _lib.ptr(out),
-                                                      self._st()), 'stof_sincnet_train_conv')
+        _lib.call('stof_sincnet_train_conv', layer, src, n, L, blob, bias, out, self._st())
         return out
 
     def stats(self, z, n, L, ch, gamma, beta, run_mean, run_var):
         """-> (stat [4, ch] float64, new running_mean, new running_var)"""
-        lib, desc, ws = _lib.lib(), self._desc(), self._stats_ws()
+        desc, ws = self._desc(), self._stats_ws()
         stat = torch.empty((4, ch), dtype=torch.float64, device=self.dev)
         new_mean = torch.empty(ch, dtype=torch.float32, device=self.dev)
         new_var = torch.empty(ch, dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_sincnet_train_stats(ctypes.byref(desc), _lib.ptr(z), n, L, ch, _lib.ptr(gamma), _lib.ptr(beta),
-                                                _lib.ptr(run_mean), _lib.ptr(run_var), self.momentum, _lib.ptr(stat), _lib.ptr(new_mean),
-                                                _lib.ptr(new_var), _lib.ptr(ws), ws.numel(), self._st()), 'stof_sincnet_train_stats')
+        _lib.call('stof_sincnet_train_stats', desc, z, n, L, ch, gamma, beta, run_mean, run_var, self.momentum, stat, new_mean, new_var, ws,
+                  ws.numel(), self._st())
         return stat, new_mean, new_var
 
     def apply(self, z, n, L, ch, stat):
         out = self.buffer(n, L) if ch == C else torch.empty(n * L, dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().stof_sincnet_train_apply(_lib.ptr(z), n, L, ch, _lib.ptr(stat), _lib.ptr(out), self._st()),
-                   'stof_sincnet_train_apply')
+        _lib.call('stof_sincnet_train_apply', z, n, L, ch, stat, out, self._st())
         return out
 
     def bn_bwd(self, da, a, z, stat, gamma, n, L, ch, dgamma, dbeta):
         """-> dz (GAP layout / flat); dgamma, dbeta are written in place"""
         ws = self._stats_ws()
         dz = self.buffer(n, L) if ch == C else torch.empty(n * L, dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().stof_sincnet_train_bn_bwd(_lib.ptr(da), _lib.ptr(a), _lib.ptr(z), _lib.ptr(stat), _lib.ptr(gamma), n, L, ch,
-                                                        _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dz), _lib.ptr(ws), ws.numel(),
-                                                        self._st()), 'stof_sincnet_train_bn_bwd')
+        _lib.call('stof_sincnet_train_bn_bwd', da, a, z, stat, gamma, n, L, ch, dgamma, dbeta, dz, ws, ws.numel(), self._st())
         return dz
 
     def conv_wgrad(self, layer, a_prev, dz, n, L, dw, db):
-        lib = _lib.lib()
-        ws = self._scratch('_sn_wgrad_ws', lib.stof_sincnet_train_conv_wgrad_workspace_bytes(1))
-        _lib.check(lib.stof_sincnet_train_conv_wgrad(layer, _lib.ptr(a_prev), _lib.ptr(dz), n, L, _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws),
-                                                     ws.numel(), self._st()), 'stof_sincnet_train_conv_wgrad')
+        ws = self._scratch('_sn_wgrad_ws', _lib.call('stof_sincnet_train_conv_wgrad_workspace_bytes', 1))
+        _lib.call('stof_sincnet_train_conv_wgrad', layer, a_prev, dz, n, L, dw, db, ws, ws.numel(), self._st())
 
     def conv_dgrad(self, layer, dz, n, L, image):
         da = self.buffer(n, L)
-        _lib.check(_lib.lib().stof_sincnet_train_conv_dgrad(layer, _lib.ptr(dz), n, L, _lib.ptr(image), _lib.ptr(da), self._st()),
-                   'stof_sincnet_train_conv_dgrad')
+        _lib.call('stof_sincnet_train_conv_dgrad', layer, dz, n, L, image, da, self._st())
         return da
 
     def out_wgrad(self, a2, dz3, n, L, dw, db):
-        lib = _lib.lib()
-        ws = self._scratch('_sn_out_ws', lib.stof_sincnet_train_out_wgrad_workspace_bytes())
-        _lib.check(lib.stof_sincnet_train_out_wgrad(_lib.ptr(a2), _lib.ptr(dz3), n, L, _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), ws.numel(),
-                                                    self._st()), 'stof_sincnet_train_out_wgrad')
+        ws = self._scratch('_sn_out_ws', _lib.call('stof_sincnet_train_out_wgrad_workspace_bytes'))
+        _lib.call('stof_sincnet_train_out_wgrad', a2, dz3, n, L, dw, db, ws, ws.numel(), self._st())
 
     def out_dgrad(self, dz3, w3, n, L):
         da = self.buffer(n, L)
-        _lib.check(_lib.lib().stof_sincnet_train_out_dgrad(_lib.ptr(dz3), _lib.ptr(w3), n, L, _lib.ptr(da), self._st()),
-                   'stof_sincnet_train_out_dgrad')
+        _lib.call('stof_sincnet_train_out_dgrad', dz3, w3, n, L, da, self._st())
         return da
 
     def bank_grad(self, x, dz0, n, L):
         """-> G [128, 1023] = d loss / d filter bank"""
-        lib = _lib.lib()
-        ws = self._scratch('_sn_bank_ws', lib.stof_sincnet_train_bank_grad_workspace_bytes())
+        ws = self._scratch('_sn_bank_ws', _lib.call('stof_sincnet_train_bank_grad_workspace_bytes'))
         G = torch.empty((C, TAPS[0]), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_sincnet_train_bank_grad(_lib.ptr(x), _lib.ptr(dz0), n, L, _lib.ptr(G), _lib.ptr(ws), ws.numel(), self._st()),
-                   'stof_sincnet_train_bank_grad')
+        _lib.call('stof_sincnet_train_bank_grad', x, dz0, n, L, G, ws, ws.numel(), self._st())
         return G
 
     def band_grad(self, low, band, G, dlow, dband):
         desc = self._desc()
-        _lib.check(_lib.lib().stof_sincnet_train_band_grad(ctypes.byref(desc), _lib.ptr(low), _lib.ptr(band), _lib.ptr(G), _lib.ptr(dlow),
-                                                           _lib.ptr(dband), self._st()), 'stof_sincnet_train_band_grad')
+        _lib.call('stof_sincnet_train_band_grad', desc, low, band, G, dlow, dband, self._st())
 
     def in_dgrad(self, dz0, blob, n, L, dx):
-        _lib.check(_lib.lib().stof_sincnet_train_in_dgrad(_lib.ptr(dz0), _lib.ptr(blob), n, L, _lib.ptr(dx), self._st()),
-                   'stof_sincnet_train_in_dgrad')
+        _lib.call('stof_sincnet_train_in_dgrad', dz0, blob, n, L, dx, self._st())
 
     # ------------------------------------------------------------------------------------------------------- the step
     def out_shape(self, n, L):

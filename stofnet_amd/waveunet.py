@@ -149,6 +149,7 @@ class WaveUnet(_KernelRoute, nn.Module):
         graph when one is recorded: its backward fills the gradient of every parameter (and of x, if it asks for one) in
         exact fp32.  BatchNorm uses batch statistics and the running statistics are updated, also under no_grad.  Not
         chunked by `max_workspace_bytes`: the batch statistics and the backward need every activation of the whole batch."""
+        from ._train_boundary import commit_running_stats, train_engine
         from .waveunet_training import WaveUnetFunction, WaveUnetTrainEngine
         if not self.training:
             raise NotImplementedError("WaveUnet: train_route='kernels' serves train mode only (batch statistics); eval-mode "
@@ -159,22 +160,14 @@ class WaveUnet(_KernelRoute, nn.Module):
         if N * (L >> n) == 1:                               # torch's BatchNorm check, word for word, before anything is touched
             raise ValueError(f'Expected more than 1 value per channel when training, got input size {torch.Size([N, 16 * n, L >> n])}')
         bns = [blk.main[1] for blk in self.encoder] + [self.middle[1]] + [blk.main[1] for blk in self.decoder]
-        engines = self.__dict__.setdefault('_train_engines', {})
-        key = str(x.device)
-        if key not in engines:
-            engines[key] = WaveUnetTrainEngine(x.device, n)
-        engine = engines[key]
+        engine = train_engine(self, str(x.device), lambda: WaveUnetTrainEngine(x.device, n))
         engine.eps = [float(bn.eps) for bn in bns]
         engine.momentum = [float(bn.momentum) for bn in bns]
         engine.running = [(bn.running_mean, bn.running_var) for bn in bns]
         names, params = zip(*self.named_parameters())
         y = WaveUnetFunction.apply(x, engine, names, *params)
         if N:
-            with torch.no_grad():                # on the host side: `copy_` bumps the buffers' versions (the eval-mode blob's key)
-                for bn, (mean, var) in zip(bns, engine.new_running):
-                    bn.running_mean.copy_(mean)
-                    bn.running_var.copy_(var)
-                    bn.num_batches_tracked.add_(1)
+            commit_running_stats(bns, engine.new_running)
         return y
 
     def forward(self, x):

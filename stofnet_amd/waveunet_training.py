@@ -35,7 +35,7 @@ def _constants():
     global _CONSTANTS
     if _CONSTANTS is None:
         v = (ctypes.c_int64 * 10)()
-        _lib.check(_lib.lib().stof_waveunet_train_constants(v), 'stof_waveunet_train_constants')
+        _lib.call('stof_waveunet_train_constants', v)
         k = [int(q) for q in v]
         _CONSTANTS = {
             # rows per partial, at the least, of the chunked reductions, and the number of partials at the most: beyond
@@ -83,8 +83,7 @@ def interp_table(M):
     i0, i1 = np.empty(2 * M, np.int32), np.empty(2 * M, np.int32)
     l0, l1 = np.empty(2 * M, np.float32), np.empty(2 * M, np.float32)
     lo, hi = np.empty(M, np.int32), np.empty(M, np.int32)
-    _lib.check(_lib.lib().stof_waveunet_interp_table(M, *[ctypes.c_void_p(a.ctypes.data) for a in (i0, i1, l0, l1, lo, hi)]),
-               'stof_waveunet_interp_table')
+    _lib.call('stof_waveunet_interp_table', M, *[ctypes.c_void_p(a.ctypes.data) for a in (i0, i1, l0, l1, lo, hi)])
     return i0, i1, l0, l1, lo, hi
 
 
@@ -120,22 +119,19 @@ class WaveUnetTrainEngine(SavedStepEngine):
         return torch.empty(shape, dtype=torch.float32, device=self.dev)
 
     def _stats_ws(self):
-        return self._scratch('_wu_stats_ws', _lib.lib().stof_waveunet_train_stats_workspace_bytes())
+        return self._scratch('_wu_stats_ws', _lib.call('stof_waveunet_train_stats_workspace_bytes'))
 
     # ------------------------------------------------------------------------------------------------ weight images
     def pack_frag(self, w, flip):
         """weight [cout, cin, taps] -> its fragment image (flip: the data gradient's)"""
         cout, cin, taps = (int(v) for v in w.shape)
-        lib = _lib.lib()
-        img = self._new(int(lib.stof_waveunet_train_frag_floats(cin, cout, taps, int(flip))))
-        _lib.check(lib.stof_waveunet_train_pack_frag(_lib.ptr(w), cin, cout, taps, int(flip), _lib.ptr(img), self._st()),
-                   'stof_waveunet_train_pack_frag')
+        img = self._new(int(_lib.call('stof_waveunet_train_frag_floats', cin, cout, taps, int(flip))))
+        _lib.call('stof_waveunet_train_pack_frag', w, cin, cout, taps, int(flip), img, self._st())
         return img
 
     def pack_in(self, w, b):
         img = self._new(256)
-        _lib.check(_lib.lib().stof_waveunet_train_pack_in(_lib.ptr(w), _lib.ptr(b), _lib.ptr(img), self._st()),
-                   'stof_waveunet_train_pack_in')
+        _lib.call('stof_waveunet_train_pack_in', w, b, img, self._st())
         return img
 
     def _in_image(self, w, b):
@@ -149,15 +145,13 @@ class WaveUnetTrainEngine(SavedStepEngine):
     def in_conv(self, x, image):
         n, L = x.shape
         z = self._new(n, L, 16)
-        _lib.check(_lib.lib().stof_waveunet_train_in_conv(_lib.ptr(x), n, L, _lib.ptr(image), _lib.ptr(z), self._st()),
-                   'stof_waveunet_train_in_conv')
+        _lib.call('stof_waveunet_train_in_conv', x, n, L, image, z, self._st())
         return z
 
     def conv(self, src, low, n, Lout, cin, cu, cout, taps, mode, frag, bias):
         """-> [n, Lout, cout]: the convolution of the virtual input (`mode`) with the image `frag` (+ bias)"""
         out = self._new(n, Lout, cout)
-        _lib.check(_lib.lib().stof_waveunet_train_conv(_lib.ptr(src), _lib.ptr(low), n, Lout, cin, cu, cout, taps, mode, _lib.ptr(frag),
-                                                       _lib.ptr(bias), _lib.ptr(out), self._st()), 'stof_waveunet_train_conv')
+        _lib.call('stof_waveunet_train_conv', src, low, n, Lout, cin, cu, cout, taps, mode, frag, bias, out, self._st())
         return out
 
     def stats(self, z, gamma, beta, run_mean, run_var, eps, momentum):
@@ -166,36 +160,29 @@ class WaveUnetTrainEngine(SavedStepEngine):
         rows, ws = z.numel() // ch, self._stats_ws()
         stat = torch.empty((4, ch), dtype=torch.float64, device=self.dev)
         new_mean, new_var = self._new(ch), self._new(ch)
-        _lib.check(_lib.lib().stof_waveunet_train_stats(_lib.ptr(z), rows, ch, _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(run_mean),
-                                                        _lib.ptr(run_var), float(eps), float(momentum), _lib.ptr(stat), _lib.ptr(new_mean),
-                                                        _lib.ptr(new_var), _lib.ptr(ws), ws.numel(), self._st()),
-                   'stof_waveunet_train_stats')
+        _lib.call('stof_waveunet_train_stats', z, rows, ch, gamma, beta, run_mean, run_var, float(eps), float(momentum), stat, new_mean, new_var, ws,
+                  ws.numel(), self._st())
         return stat, new_mean, new_var
 
     def apply(self, z, stat):
         ch = int(z.shape[-1])
         a = torch.empty_like(z)
-        _lib.check(_lib.lib().stof_waveunet_train_apply(_lib.ptr(z), z.numel() // ch, ch, _lib.ptr(stat), _lib.ptr(a), self._st()),
-                   'stof_waveunet_train_apply')
+        _lib.call('stof_waveunet_train_apply', z, z.numel() // ch, ch, stat, a, self._st())
         return a
 
     def head(self, o, x, w, b):
         n, L = x.shape
         y = self._new(n, L)
-        _lib.check(_lib.lib().stof_waveunet_train_head(_lib.ptr(o), _lib.ptr(x), n, L, _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), self._st()),
-                   'stof_waveunet_train_head')
+        _lib.call('stof_waveunet_train_head', o, x, n, L, w, b, y, self._st())
         return y
 
     def head_bwd(self, dy, y, o, x, w, dw, db, want_dx):
         """-> (do [N, L, 16], the head's term of dx [N, L] or None); dw [17], db [1] are written in place"""
         n, L = x.shape
-        lib = _lib.lib()
-        ws = self._scratch('_wu_head_ws', lib.stof_waveunet_train_head_bwd_workspace_bytes())
+        ws = self._scratch('_wu_head_ws', _lib.call('stof_waveunet_train_head_bwd_workspace_bytes'))
         dout = self._new(n, L, 16)
         dxh = self._new(n, L) if want_dx else None
-        _lib.check(lib.stof_waveunet_train_head_bwd(_lib.ptr(dy), _lib.ptr(y), _lib.ptr(o), _lib.ptr(x), n, L, _lib.ptr(w), _lib.ptr(dout),
-                                                    _lib.ptr(dxh), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), ws.numel(), self._st()),
-                   'stof_waveunet_train_head_bwd')
+        _lib.call('stof_waveunet_train_head_bwd', dy, y, o, x, n, L, w, dout, dxh, dw, db, ws, ws.numel(), self._st())
         return dout, dxh
 
     def bn_bwd(self, da, a, z, stat, dgamma, dbeta):
@@ -203,24 +190,17 @@ class WaveUnetTrainEngine(SavedStepEngine):
         ch = int(z.shape[-1])
         ws = self._stats_ws()
         dz = torch.empty_like(z)
-        _lib.check(_lib.lib().stof_waveunet_train_bn_bwd(_lib.ptr(da), _lib.ptr(a), _lib.ptr(z), _lib.ptr(stat), z.numel() // ch, ch,
-                                                         _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dz), _lib.ptr(ws), ws.numel(),
-                                                         self._st()), 'stof_waveunet_train_bn_bwd')
+        _lib.call('stof_waveunet_train_bn_bwd', da, a, z, stat, z.numel() // ch, ch, dgamma, dbeta, dz, ws, ws.numel(), self._st())
         return dz
 
     def conv_wgrad(self, src, low, dz, n, Lout, cin, cu, cout, taps, mode, dw, db):
-        lib = _lib.lib()
-        ws = self._scratch('_wu_wgrad_ws', lib.stof_waveunet_train_wgrad_workspace_bytes(n, Lout, cin, cout, taps))
-        _lib.check(lib.stof_waveunet_train_wgrad(_lib.ptr(src), _lib.ptr(low), _lib.ptr(dz), n, Lout, cin, cu, cout, taps, mode,
-                                                 _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), ws.numel(), self._st()),
-                   'stof_waveunet_train_wgrad')
+        ws = self._scratch('_wu_wgrad_ws', _lib.call('stof_waveunet_train_wgrad_workspace_bytes', n, Lout, cin, cout, taps))
+        _lib.call('stof_waveunet_train_wgrad', src, low, dz, n, Lout, cin, cu, cout, taps, mode, dw, db, ws, ws.numel(), self._st())
 
     def in_wgrad(self, x, dz, dw, db):
         n, L = x.shape
-        lib = _lib.lib()
-        ws = self._scratch('_wu_in_ws', lib.stof_waveunet_train_in_wgrad_workspace_bytes())
-        _lib.check(lib.stof_waveunet_train_in_wgrad(_lib.ptr(x), _lib.ptr(dz), n, L, _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), ws.numel(),
-                                                    self._st()), 'stof_waveunet_train_in_wgrad')
+        ws = self._scratch('_wu_in_ws', _lib.call('stof_waveunet_train_in_wgrad_workspace_bytes'))
+        _lib.call('stof_waveunet_train_in_wgrad', x, dz, n, L, dw, db, ws, ws.numel(), self._st())
 
     def conv_dgrad(self, dz, n, Lout, cin, cout, taps, image):
         """dz [n, Lout, cout] -> the gradient of the virtual input [n, Lout, cin]: the forward kernel on the flipped image"""
@@ -229,21 +209,18 @@ class WaveUnetTrainEngine(SavedStepEngine):
     def interp_t(self, g, n, M, cu):
         """g [n, 2 M, cg] -> [n, M, cu]: the transpose of the x2 interpolation on the first cu channels"""
         dlow = self._new(n, M, cu)
-        _lib.check(_lib.lib().stof_waveunet_train_interp_t(_lib.ptr(g), n, M, int(g.shape[-1]), cu, _lib.ptr(dlow), self._st()),
-                   'stof_waveunet_train_interp_t')
+        _lib.call('stof_waveunet_train_interp_t', g, n, M, int(g.shape[-1]), cu, dlow, self._st())
         return dlow
 
     def skip_sum(self, gdec, genc, n, L, cu, cs):
         """-> [n, L, cs] = gdec[..., cu:] at every position, then + genc [n, L / 2, cs] at even positions"""
         out = self._new(n, L, cs)
-        _lib.check(_lib.lib().stof_waveunet_train_skip_sum(_lib.ptr(gdec), _lib.ptr(genc), n, L, cu, cs, _lib.ptr(out), self._st()),
-                   'stof_waveunet_train_skip_sum')
+        _lib.call('stof_waveunet_train_skip_sum', gdec, genc, n, L, cu, cs, out, self._st())
         return out
 
     def in_dgrad(self, dz, w, dxh, dx):
         n, L = dx.shape
-        _lib.check(_lib.lib().stof_waveunet_train_in_dgrad(_lib.ptr(dz), _lib.ptr(w), _lib.ptr(dxh), n, L, _lib.ptr(dx), self._st()),
-                   'stof_waveunet_train_in_dgrad')
+        _lib.call('stof_waveunet_train_in_dgrad', dz, w, dxh, n, L, dx, self._st())
 
     # ------------------------------------------------------------------------------------------------------- the step
     def out_shape(self, n, L):

@@ -89,20 +89,13 @@ class _ZonziniNet(_PackedKernels, nn.Module):
         """y [N, 1] float32 on the gfx950 training kernels (zonzini_training.py), with an autograd graph: its backward fills
         the gradient of every parameter (and of x, if it asks for one) in exact fp32.  Not chunked by `max_workspace_bytes`:
         the backward needs every activation of the whole batch."""
+        from ._train_boundary import fp32_device_params, train_engine
         from .zonzini_training import ZonziniFunction, ZonziniTrainEngine
         with torch.no_grad():                                # the checks of an inference call, minus the graph condition
             self._check_input(x)
-        names, params = zip(*self.named_parameters())
-        for p in params:
-            if p.dtype != torch.float32:
-                raise TypeError(f'{type(self).__name__}: parameters must be float32 (got {p.dtype}); the gfx950 kernels are '
-                                'fp32 only')
-            _lib.require_device(p, 'parameter')
-        engines = self.__dict__.setdefault('_train_engines', {})
-        key = str(x.device)
-        if key not in engines:
-            engines[key] = ZonziniTrainEngine(x.device, self.VARIANT)
-        return ZonziniFunction.apply(x, engines[key], names, *params)
+        names, params = fp32_device_params(self, type(self).__name__)
+        engine = train_engine(self, str(x.device), lambda: ZonziniTrainEngine(x.device, self.VARIANT))
+        return ZonziniFunction.apply(x, engine, names, *params)
 
     def forward(self, x):
         if self.train_route not in (None, 'kernels', 'aten'):

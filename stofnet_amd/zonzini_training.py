@@ -57,7 +57,6 @@ class ZonziniTrainEngine(SavedStepEngine):
         self.cpad = tuple((c + 3) & ~3 for c in self.channels)
         self.names = param_names(len(self.channels))
         self.label = 'ZonziniNetSmall' if self.variant == _lib.ZONZINI_SMALL else 'ZonziniNetLarge'
-        self._blob = None           # (versions of every parameter, the packed blob of the forward kernels)
 
     def out_shape(self, n, L):
         return (n, 1)
@@ -66,28 +65,19 @@ class ZonziniTrainEngine(SavedStepEngine):
         return _lib.ZonziniDesc(self.variant, 0)
 
     def _packed(self, p):
-        """The forward kernels' blob of this step's parameters, packed again when one of them changed."""
-        version = tuple((p[k].data_ptr(), p[k]._version) for k in self.names)
-        if self._blob is None or self._blob[0] != version:
-            lib, desc = _lib.lib(), self._desc()
-            nbytes = int(lib.stof_zonzini_packed_bytes(ctypes.byref(desc)))
-            blob = self._blob[1] if self._blob is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-            ptrs = (ctypes.c_void_p * len(self.names))(*[p[k].data_ptr() for k in self.names])
-            _lib.check(lib.stof_zonzini_train_pack(ctypes.byref(desc), ptrs, _lib.ptr(blob), nbytes, self._st()),
-                       'stof_zonzini_train_pack')
-            self._blob = (version, blob)
-        return self._blob[1]
+        """The forward kernels' blob of this step's parameters."""
+        desc = self._desc()
+        return self._packed_blob(p, self.names, int(_lib.call('stof_zonzini_packed_bytes', desc)), 'stof_zonzini_train_pack', desc)
 
     def _dgrad_image(self, layer, w):
-        lib, desc = _lib.lib(), self._desc()
-        img = torch.empty(lib.stof_zonzini_train_dgrad_image_floats(ctypes.byref(desc), layer), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.stof_zonzini_train_dgrad_image(ctypes.byref(desc), layer, _lib.ptr(w), _lib.ptr(img), self._st()),
-                   'stof_zonzini_train_dgrad_image')
+        desc = self._desc()
+        img = torch.empty(_lib.call('stof_zonzini_train_dgrad_image_floats', desc, layer), dtype=torch.float32, device=self.dev)
+        _lib.call('stof_zonzini_train_dgrad_image', desc, layer, w, img, self._st())
         return img
 
     def _forward_saved(self, p, frame):
         """models/zonzini.py forward -> (y [N, 1], ZonziniSaved)."""
-        lib, st, desc = _lib.lib(), self._st(), self._desc()
+        st, desc = self._st(), self._desc()
         x = self._flat_frame(frame)
         n, L = x.shape
         p = {k: v.contiguous() for k, v in p.items()}
@@ -102,42 +92,33 @@ class ZonziniTrainEngine(SavedStepEngine):
         y = torch.empty((n,), dtype=torch.float32, device=self.dev)
         a_ptrs = (ctypes.c_void_p * len(acts))(*[t.data_ptr() for t in acts])
         s_ptrs = (ctypes.c_void_p * len(sel))(*[t.data_ptr() for t in sel])
-        _lib.check(lib.stof_zonzini_train_forward(ctypes.byref(desc), _lib.ptr(x), n, L, _lib.ptr(blob), a_ptrs, s_ptrs, _lib.ptr(f),
-                                                  _lib.ptr(h), _lib.ptr(y), st), 'stof_zonzini_train_forward')
+        _lib.call('stof_zonzini_train_forward', desc, x, n, L, blob, a_ptrs, s_ptrs, f, h, y, st)
         return y.view(n, 1), ZonziniSaved(p=p, versions={k: v._version for k, v in p.items()}, x=x, acts=acts, sel=sel, f=f, h=h, y=y)
 
     def _backward_saved(self, saved, dy, g, dx=None):
         """From dy [N, 1] = dloss/dy: every parameter gradient into the tensors of `g` (name -> tensor of the parameter's shape)
         and, if `dx` [N, L] is given, the gradient with respect to the input frame into it."""
-        lib, st, p, desc = _lib.lib(), self._st(), saved.p, self._desc()
+        st, p, desc = self._st(), saved.p, self._desc()
         n, L = saved.x.shape
         self._check_versions(saved)
         layers = len(self.channels)
         dout = torch.empty((n, self.cpad[-1]), dtype=torch.float32, device=self.dev)       # df: the mean's gradient, times Lp
-        _lib.check(lib.stof_zonzini_train_head_bwd(ctypes.byref(desc), _lib.ptr(dy), _lib.ptr(saved.f), _lib.ptr(saved.h),
-                                                   _lib.ptr(p['fc1.weight']), _lib.ptr(p['fc2.weight']), _lib.ptr(g['fc1.weight']),
-                                                   _lib.ptr(g['fc1.bias']), _lib.ptr(g['fc2.weight']), _lib.ptr(g['fc2.bias']),
-                                                   _lib.ptr(dout), n, st), 'stof_zonzini_train_head_bwd')
+        _lib.call('stof_zonzini_train_head_bwd', desc, dy, saved.f, saved.h, p['fc1.weight'], p['fc2.weight'], g['fc1.weight'], g['fc1.bias'],
+                  g['fc2.weight'], g['fc2.bias'], dout, n, st)
         for l in range(layers - 1, 0, -1):
             w = p[f'conv_layers.{l}.weight']
-            ws = self._scratch('_zz_wgrad_ws', lib.stof_zonzini_train_conv_wgrad_workspace_bytes(ctypes.byref(desc), l))
-            _lib.check(lib.stof_zonzini_train_conv_wgrad(ctypes.byref(desc), l, _lib.ptr(saved.acts[l - 1]), _lib.ptr(dout),
-                                                         _lib.ptr(saved.sel[l]), _lib.ptr(g[f'conv_layers.{l}.weight']),
-                                                         _lib.ptr(g[f'conv_layers.{l}.bias']), n, L, _lib.ptr(ws), ws.numel(), st),
-                       'stof_zonzini_train_conv_wgrad')
+            ws = self._scratch('_zz_wgrad_ws', _lib.call('stof_zonzini_train_conv_wgrad_workspace_bytes', desc, l))
+            _lib.call('stof_zonzini_train_conv_wgrad', desc, l, saved.acts[l - 1], dout, saved.sel[l], g[f'conv_layers.{l}.weight'],
+                      g[f'conv_layers.{l}.bias'], n, L, ws, ws.numel(), st)
             img = self._cached(('dgrad', l), w, lambda: self._dgrad_image(l, w))
             din = torch.empty_like(saved.acts[l - 1])           # dloss/d(act l-1): its ReLU / pool is applied by the readers
-            _lib.check(lib.stof_zonzini_train_conv_dgrad(ctypes.byref(desc), l, _lib.ptr(dout), _lib.ptr(saved.sel[l]), _lib.ptr(img),
-                                                         _lib.ptr(din), n, L, st), 'stof_zonzini_train_conv_dgrad')
+            _lib.call('stof_zonzini_train_conv_dgrad', desc, l, dout, saved.sel[l], img, din, n, L, st)
             dout = din
-        ws = self._scratch('_zz_in_ws', lib.stof_zonzini_train_in_wgrad_workspace_bytes(ctypes.byref(desc)))
-        _lib.check(lib.stof_zonzini_train_in_wgrad(ctypes.byref(desc), _lib.ptr(saved.x), _lib.ptr(dout), _lib.ptr(saved.sel[0]),
-                                                   _lib.ptr(g['conv_layers.0.weight']), _lib.ptr(g['conv_layers.0.bias']), n, L,
-                                                   _lib.ptr(ws), ws.numel(), st), 'stof_zonzini_train_in_wgrad')
+        ws = self._scratch('_zz_in_ws', _lib.call('stof_zonzini_train_in_wgrad_workspace_bytes', desc))
+        _lib.call('stof_zonzini_train_in_wgrad', desc, saved.x, dout, saved.sel[0], g['conv_layers.0.weight'], g['conv_layers.0.bias'], n, L, ws,
+                  ws.numel(), st)
         if dx is not None:
-            _lib.check(lib.stof_zonzini_train_in_dgrad(ctypes.byref(desc), _lib.ptr(dout), _lib.ptr(saved.sel[0]),
-                                                       _lib.ptr(p['conv_layers.0.weight']), _lib.ptr(dx), n, L, st),
-                       'stof_zonzini_train_in_dgrad')
+            _lib.call('stof_zonzini_train_in_dgrad', desc, dout, saved.sel[0], p['conv_layers.0.weight'], dx, n, L, st)
 
 
 class ZonziniFunction(EndsFunction):
