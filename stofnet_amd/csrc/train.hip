@@ -1885,6 +1885,11 @@ __global__ __launch_bounds__(256) void loss_target_kernel(const long long* __res
         atomicMax(reinterpret_cast<int*>(tmax), __float_as_int(mx));
 }
 
+// block partials of loss_grad_kernel and the ticket that finds its last block (one loss kernel at a time per device)
+constexpr unsigned LOSS_MAX_BLOCKS = 512;
+__device__ double g_loss_part[LOSS_MAX_BLOCKS];
+__device__ unsigned g_loss_ticket = 0;
+
 // loss[0] += sum (pred - s*target)^2 / NM + lambda * sum |pred| / NM ; dpred = 2 (pred - s*target)/NM + lambda sign(pred)/NM
 __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ pred, float* __restrict__ target,
                                                         const float* __restrict__ tmax, float amplitude, float lambda,
@@ -1919,9 +1924,26 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
     __shared__ double wsum[4];
+    __shared__ bool last;
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = part;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss, (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
+    // Block partials meet in a FIXED order, so the loss is the same bits run after run (atomic adds of doubles on one
+    // address differed in the last ulp with the order the blocks happened to finish in): every block parks its partial,
+    // the block that draws the last ticket adds them up by index.  The ticket counter wraps back to 0 by itself.
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&g_loss_part[blockIdx.x], (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        last = atomicInc(&g_loss_ticket, gridDim.x - 1) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last || threadIdx.x >= 64) return;
+    __threadfence();
+    double tot = 0.0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += 64)
+        tot += __hip_atomic_load(&g_loss_part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+    if (threadIdx.x == 0) loss[0] += tot;
 }
 
 // torch.optim.AdamW step (decoupled weight decay), one flat parameter vector
@@ -2516,8 +2538,8 @@ extern "C" int stof_train_loss_grad(const float* pred, float* target, const floa
     if (!pred || !target || !tmax || !dpred || !loss) return STOF_ERR_BAD_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (hipMemsetAsync(loss, 0, sizeof(double), s) != hipSuccess) return STOF_ERR_HIP;
-    // one double atomic per block on ONE address (~90 per microsecond): 512 grid-striding blocks, not thousands
-    const unsigned lblocks = blocks_for(N * M) < 512u ? blocks_for(N * M) : 512u;
+    // one parked partial per block, added up in index order by the last one: 512 grid-striding blocks, not thousands
+    const unsigned lblocks = blocks_for(N * M) < LOSS_MAX_BLOCKS ? blocks_for(N * M) : LOSS_MAX_BLOCKS;
     hipLaunchKernelGGL(loss_grad_kernel, dim3(lblocks), dim3(256), 0, s, pred, target, tmax, amplitude, lambda,
                        (long long)(N * M), grad_scale, dpred, loss);
     return hipGetLastError() == hipSuccess ? STOF_OK : STOF_ERR_HIP;

@@ -256,12 +256,21 @@ class StofNet(nn.Module):
         """Inference for a semi_global_scale other than 80, a num_blocks other than 13, a body kernel other than 7, a
         num_features other than 64 or more than one input channel (models/stofnet.py:11 accepts any): every layer on the
         channel-last MFMA kernels, activations dropped as soon as the next layer has consumed them.  'auto' maps to the
-        exact fp32 mode here (the range guard lives in the fused sweep)."""
+        exact fp32 mode here (the fp32 re-run lives in the fused sweep).  'f16x3' keeps the fused route's contract: the
+        range-guard word `raise_if_overflow()` reads is ORed on the device, with no host sync here.  An activation beyond the
+        fp16 range splits into (inf, -inf), whose products sum to NaN; on this route nothing between a split and the
+        prediction turns NaN back into a number (the leaky ReLU is a select, every residual add keeps it, and every stage feeds
+        a convolution on the way to conv_last), so a non-finite scan of the prediction sees every overflow
+        (tests/test_gpu_range_contract.py drives one from every interior stage)."""
         if x.shape[0] == 0:
             return torch.empty((0, 1, x.shape[-1] * int(self.upsample_factor)), dtype=torch.float32, device=x.device)
         eng = self._engine(x.device, 'f16x3' if self.precision == 'f16x3' else 'fp32')
         with torch.cuda.device(x.device):
             pred, _ = eng._forward_saved({n: p.detach() for n, p in self.named_parameters()}, x, keep=False)
+            if self.precision == 'f16x3':
+                if self._status is None or self._status.device != x.device:
+                    self._status = torch.zeros(1, dtype=torch.int32, device=x.device)
+                self._status |= torch.isfinite(pred).all().logical_not()      # sticky until raise_if_overflow(), as the fused route's
         return pred.view(x.shape[0], 1, -1)
 
     def _forward_with_graph(self, x):
