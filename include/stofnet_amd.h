@@ -641,6 +641,93 @@ int stof_kuleshov_forward(const stof_kuleshov_desc* desc, const float* x, int64_
                           const void* packed, float* y, float* bottleneck, float* final_in, float* final_out,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Kuleshov training (csrc/kuleshov_train.hip; the host side is stofnet_amd/kuleshov_training.py): one entry per stage,
+ * exact fp32 with double where the file says so, no float atomic: two runs are bitwise equal.  Activations and gradients
+ * are channel-last fp32 device arrays; widths are multiples of 128 up to 1024, taps 9, 17, 33 or 65.  A concatenation
+ * buffer is addressed by a pointer to its first served row and the floats between waveforms (`*_n_stride`).  Every
+ * argument is checked before the first device call: STOF_ERR_BAD_ARG outside the served range (0 from the size
+ * functions), STOF_ERR_WORKSPACE for a short workspace, STOF_ERR_UNSUPPORTED where 32-bit indexing would overflow.
+ *
+ * Dropout: the keep-mask is a pure function of (seed, call, rank, site, row n, element e = t C + c of the layer's
+ * unshuffled [position][channel] output): Philox4x32-10 with key (seed lo, seed hi), counter (e >> 2, n, call,
+ * (rank << 3) | site), word e & 3; site 0 = the bottleneck, 1..4 = up 0..3; kept when word >= floor(p 2^32), kept
+ * values are scaled by 1.0f / (1.0f - p); p in [0, 1).  It is never stored.
+ * ------------------------------------------------------------------------- */
+/* Host only, no device: keep[count] = 1 where element e = 0 .. count - 1 of row n is kept.                            */
+int stof_kuleshov_dropout_keep(uint64_t seed, uint32_t call, uint32_t rank, int32_t site, int64_t n, int64_t count, double p,
+                               uint8_t* keep);
+/* out[8]: rows per partial / partials at the most of the statistics, BN backward and bias sums (0, 1), the wide
+ * convolutions' weight gradient (2, 3), final_conv's (4, 5) and down_conv0's (6, 7).                                  */
+int stof_kuleshov_train_constants(int64_t* out);
+/* The fragment image of weight w [cout][cin][taps] for stof_kuleshov_train_conv: kind 0 the forward's, 1 the stride-1
+ * data gradient's, 2 and 3 the even and odd tap class of the stride-2 data gradient's.                               */
+size_t stof_kuleshov_train_frag_floats(int32_t cin, int32_t cout, int32_t taps, int32_t kind);
+int stof_kuleshov_train_pack_frag(const float* w, int32_t cin, int32_t cout, int32_t taps, int32_t kind, float* frag, void* stream);
+/* final_conv.weight [2][128][9] -> image [2][9][128]; output_fc.weight [O][2 F] -> its fragment image                 */
+int stof_kuleshov_train_pack_final(const float* w, float* image, void* stream);
+size_t stof_kuleshov_train_fc_frag_floats(const stof_kuleshov_desc* desc);
+int stof_kuleshov_train_pack_fc(const stof_kuleshov_desc* desc, const float* w, float* frag, void* stream);
+/* down_conv0: u [N][D0][128] = leaky0.01(conv(x[:, :L]) + b), w [128][1][65]                                          */
+int stof_kuleshov_train_down0(const float* x, int64_t x_row_stride, int64_t N, int64_t L, const float* w, const float* b, float* u,
+                              void* stream);
+/* out[n][t][c] = sum over the `rows` x cin floats of `in` from row stride t on, times the image (+ bias, if not NULL;
+ * through leaky0.01 if slope01), at out + n out_n_stride + t out_t_stride + c                                         */
+int stof_kuleshov_train_conv(const float* in, int64_t in_n_stride, int64_t N, int64_t Lout, int32_t cin, int32_t cout, int32_t rows,
+                             int32_t stride, const float* frag, const float* bias, int32_t slope01, float* out, int64_t out_n_stride,
+                             int64_t out_t_stride, void* stream);
+size_t stof_kuleshov_train_stats_workspace_bytes(void);
+/* z [rows, ch] -> stat [4][ch] double (mean, rstd, s, t) and the blended running statistics (not in place)            */
+int stof_kuleshov_train_stats(const float* z, int64_t rows, int32_t ch, const float* gamma, const float* beta, const float* run_mean,
+                              const float* run_var, double eps, double momentum, double* stat, float* new_mean, float* new_var,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* a = leaky0.2(u s + t) at out + n out_n_stride + t ch + c                                                            */
+int stof_kuleshov_train_apply_down(const float* u, int64_t N, int64_t D, int32_t ch, const double* stat, float* out, int64_t out_n_stride,
+                                   void* stream);
+/* a = (z s + t) keep scale of z [N][U][ch] at the pixel-shuffled address out + n out_n_stride + (2 t + (c & 1)) ch / 2 + c / 2 */
+int stof_kuleshov_train_apply_up(const float* z, int64_t N, int64_t U, int32_t ch, const double* stat, uint64_t seed, uint32_t call,
+                                 uint32_t rank, int32_t site, double p, float* out, int64_t out_n_stride, void* stream);
+/* out [N][B][512] = leaky0.2(z keep scale), site 0                                                                    */
+int stof_kuleshov_train_apply_bott(const float* z, int64_t N, int64_t B, uint64_t seed, uint32_t call, uint32_t rank, double p, float* out,
+                                   void* stream);
+/* final_conv and output_fc as in inference: cat3 [N][Lc3][128] -> flat [N][Kp] (kept for the backward), y [N][O]       */
+int stof_kuleshov_train_tail(const stof_kuleshov_desc* desc, const float* cat3, int64_t N, const float* final_image, const float* final_bias,
+                             const float* fc_frag, const float* fc_bias, float* flat, float* y, void* stream);
+/* output_fc: dflat [N][Kp] = dy w, dw [O][2 F] = dy^T flat, db [O]                                                    */
+int stof_kuleshov_train_fc_bwd(const stof_kuleshov_desc* desc, const float* dy, const float* flat, const float* w, int64_t N, float* dflat,
+                               float* dw, float* db, void* stream);
+size_t stof_kuleshov_train_final_bwd_workspace_bytes(void);
+/* final_conv: dcat3 [N][Lc3][128], dw [2][128][9], db [2] from dflat and cat3                                         */
+int stof_kuleshov_train_final_bwd(const stof_kuleshov_desc* desc, const float* dflat, const float* cat3, const float* w, int64_t N,
+                                  float* dcat3, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+/* g [N][U][ch] = (the gradient at the shuffled address of dcat) keep scale                                            */
+int stof_kuleshov_train_gather_up(const float* dcat, int64_t dcat_n_stride, int64_t N, int64_t U, int32_t ch, uint64_t seed, uint32_t call,
+                                  uint32_t rank, int32_t site, double p, float* g, void* stream);
+/* g [N][D][ch] = (dskip, then + dnext [N][D][ch] if not NULL) (a > 0 ? 1 : 0.2); dskip and a are rows of concatenation buffers */
+int stof_kuleshov_train_gather_down(const float* dskip, int64_t dskip_n_stride, const float* dnext, const float* a, int64_t a_n_stride,
+                                    int64_t N, int64_t D, int32_t ch, float* g, void* stream);
+/* the bottleneck: dz [N][B][512] = g (z keep > 0 ? 1 : 0.2) keep scale                                                */
+int stof_kuleshov_train_gather_bott(const float* g, const float* z, int64_t N, int64_t B, uint64_t seed, uint32_t call, uint32_t rank,
+                                    double p, float* dz, void* stream);
+/* g, zu [rows, ch] -> dgamma, dbeta [ch], dz [rows, ch] (slope01: times the leaky0.01 decision zu > 0); workspace as
+ * for the statistics                                                                                                  */
+int stof_kuleshov_train_bn_bwd(const float* g, const float* zu, const double* stat, int64_t rows, int32_t ch, int32_t slope01, float* dgamma,
+                               float* dbeta, float* dz, void* workspace, size_t workspace_bytes, void* stream);
+size_t stof_kuleshov_train_wgrad_workspace_bytes(int64_t N, int64_t Lout, int32_t cin, int32_t cout, int32_t taps);
+/* dw [cout][cin][taps], db [cout] from dz [N][Lout][cout] and the convolution's input (stride 1 or 2)                 */
+int stof_kuleshov_train_wgrad(const float* in, int64_t in_n_stride, const float* dz, int64_t N, int64_t Lout, int32_t cin, int32_t cout,
+                              int32_t taps, int32_t stride, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+size_t stof_kuleshov_train_dgrad_workspace_bytes(int64_t N, int64_t Lout, int32_t cout, int32_t taps, int32_t stride);
+/* out [N][Lin][cin]: the gradient of the convolution's input from dz [N][Lout][cout]; frag0: the image of kind 1
+ * (stride 1) or 2 (stride 2), frag1: of kind 3 (stride 2 only).  Input rows that no output reaches come out as zeros. */
+int stof_kuleshov_train_dgrad(const float* dz, int64_t N, int64_t Lout, int32_t cin, int32_t cout, int32_t taps, int32_t stride,
+                              const float* frag0, const float* frag1, int64_t Lin, float* out, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t stof_kuleshov_train_down0_bwd_workspace_bytes(void);
+/* down_conv0: dw [128][1][65], db [128] from x and dz [N][D0][128]; dx (NULL = not wanted): N rows of L floats          */
+int stof_kuleshov_train_down0_bwd(const float* x, int64_t x_row_stride, const float* dz, const float* w, int64_t N, int64_t L, float* dw,
+                                  float* db, float* dx, int64_t dx_row_stride, void* workspace, size_t workspace_bytes, void* stream);
+
 /* toa_rmse (utils/metrics.py:9-41): gt[N, G], es[N, E] fp32 with 0/NaN/inf as padding ->
  * out[N, 7] = (rmse, precision, recall, jaccard, tp, fp, fn).                  */
 int stof_toa_rmse(const float* gt, const float* es, int64_t N, int64_t G, int64_t E, float tol,

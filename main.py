@@ -12,7 +12,9 @@ HIP training kernels, for model=stofnet, model=edsr and model=espcn (EDSR_1D, ES
 autograd boundary, exact fp32; `train_route=kernels` runs the backward pass on the gfx950 kernels, `train_route=aten` on stock ATen
 layers; model=zonzini trains the same way with `zonzini_loss`, the reference's main.py:233-241, its route switch being
 `train_route=kernels|aten` too; model=sincnet and model=unet
-train with the same lines and switch, train-mode BatchNorm included; every other model evaluates only); launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
+train with the same lines and switch, train-mode BatchNorm included; model=kuleshov does so only with `kuleshov_train=True`
+(its Dropout masks are then a pure function of (seed, step), see stofnet_amd/kuleshov_training.py) and evaluates only without
+it; every other model evaluates only); launched under torch.distributed.run it becomes DDP (batch sharded over ranks,
 one flat gradient all-reduce per step over RCCL).  `augment=True` puts the reference's training transforms in front of every
 training step (main.py:49,54,82: CropChannelData(crop_ratio) + AddNoise(snr_db) on chirp data, AddNoise alone otherwise) as
 one launch of the device kernel (stofnet_amd/augment.py); `shuffle=True` reorders the training rows every epoch
@@ -118,7 +120,8 @@ def main(argv=None):
         model = ZonziniNetSmall() if 'chirp' in str(cfg.data_dir).lower() else ZonziniNetLarge()       # trains: train()
     elif name == 'kuleshov':                                              # main.py:137-138
         model = Kuleshov(input_length=int(frames.shape[-1]), output_length=int(frames.shape[-1]) * int(cfg.upsample_factor))
-        cfg.evaluate = True                                               # inference only on the gfx950 path
+        if not bool(getattr(cfg, 'kuleshov_train', False)):
+            cfg.evaluate = True                                           # evaluate only, unless kuleshov_train=True asks for train()
     elif name == 'sincnet':                                               # main.py:143-158
         if cfg.fs is None:
             raise ValueError('model=sincnet needs the sample rate: set the config key fs (Hz of the dataset; the sinc '
@@ -162,14 +165,14 @@ def main(argv=None):
     log = RunLog(cfg)
     if log.enabled and str(cfg.run_name) == 'local-run':
         cfg.run_name = log.name                                          # the reference names checkpoints after the wandb run
-    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name in ('stofnet', 'edsr', 'espcn', 'zonzini', 'sincnet', 'unet')) else None
+    history = train(model, frames, gt, cfg, log) if (not cfg.evaluate and name in ('stofnet', 'edsr', 'espcn', 'zonzini', 'kuleshov', 'sincnet', 'unet')) else None
     es_all, summary = evaluate(model, name, frames, gt, cfg, log)
     log.summary({'model_name': name, 'total_parameters': int(sum(p.numel() for p in model.parameters())),
                  'total_jaccard': summary.get('total_jaccard'), 'total_inference_time': summary['inference_time'],
                  'total_distance_mean': summary.get('total_distance_mean'), 'total_distance_std': summary.get('total_distance_std')})
     if history is not None:
         summary['train_history'] = history
-        if name in ('edsr', 'espcn', 'zonzini', 'sincnet', 'unet'):
+        if name in ('edsr', 'espcn', 'zonzini', 'kuleshov', 'sincnet', 'unet'):
             summary['train_route'], summary['train_precision'] = model.train_route, 'fp32'
     if int(os.environ.get('RANK', '0')) == 0:
         print(json.dumps(summary))
@@ -215,7 +218,8 @@ def train(model, frames, gt, cfg, log=None):
     SincNet (model=sincnet, upsample_factor 1) takes them too (stofnet_amd/sincnet_training.py): its BatchNorm layers run in train
     mode, so every step also updates their running statistics, and under DDP each rank normalises with its own batch statistics
     (the reference has no SyncBatchNorm either).  WaveUnet (model=unet, upsample_factor 1) does the same through
-    stofnet_amd/waveunet_training.py.
+    stofnet_amd/waveunet_training.py, and Kuleshov (model=kuleshov with kuleshov_train=True) through
+    stofnet_amd/kuleshov_training.py, where the Dropout masks of the kernel route are drawn from (cfg.seed, step, rank).
 
     With `augment=True` every training batch goes through stofnet_amd.augment.Augment first (generator: seed = cfg.seed,
     rank = RANK, one `call` per step) and the ground truth moves with the crop window before it becomes sample indices.
@@ -231,7 +235,7 @@ def train(model, frames, gt, cfg, log=None):
     if world > 1 and not dist.is_initialized():
         dist.init_process_group('nccl', device_id=torch.device(cfg.device))
     zonzini = isinstance(model, (ZonziniNetSmall, ZonziniNetLarge))
-    routed = zonzini or isinstance(model, (EDSR_1D, ESPCN_1D, SincNet, WaveUnet))          # the baselines with a `train_route` switch
+    routed = zonzini or isinstance(model, (EDSR_1D, ESPCN_1D, Kuleshov, SincNet, WaveUnet))          # the baselines with a `train_route` switch
     tr = None if routed else StofNetTrainer(model, lr=cfg.lr, weight_decay=cfg.weight_decay, lambda_value=cfg.lambda_value,
                                             mask_amplitude=cfg.mask_amplitude, kernel_size=cfg.kernel_size, sigma=cfg.sigma,
                                             precision=cfg.train_precision)
@@ -247,6 +251,7 @@ def train(model, frames, gt, cfg, log=None):
         aug = Augment(snr_db=float(cfg.snr_db), crop_ratio=float(cfg.crop_ratio) if chirp else None, seed=int(cfg.seed),
                       rank=rank)
     best, bad, history = float('inf'), 0, []
+    restore_deterministic = None
 
     def gt_true_of(g):
         if zonzini:                                                      # `zonzini_loss` takes the ground truth as it is
@@ -270,6 +275,10 @@ def train(model, frames, gt, cfg, log=None):
             if route not in ('kernels', 'aten'):
                 raise ValueError(f"train_route must be 'kernels' or 'aten' (got {route!r})")
             model.train_route = route
+            if isinstance(model, Kuleshov) and route == 'aten':
+                # MIOpen: algorithms whose results repeat, so that two runs compare; put back when training ends (below)
+                restore_deterministic = torch.backends.cudnn.deterministic
+                torch.backends.cudnn.deterministic = True
         else:
             model.train_precision = str(cfg.train_precision)
         optimizer = torch.optim.AdamW(model.parameters(), lr=float(cfg.lr), weight_decay=float(cfg.weight_decay))
@@ -339,6 +348,8 @@ def train(model, frames, gt, cfg, log=None):
             bad += 1
         if agree_any(bad >= int(cfg.patience), device=cfg.device):       # every rank leaves at the same epoch
             break
+    if restore_deterministic is not None:
+        torch.backends.cudnn.deterministic = restore_deterministic       # the evaluation that follows chooses its algorithms as ever
     if rank == 0 and cfg.ckpt_dir:
         ckpt_dir = Path(cfg.ckpt_dir) if os.path.isabs(str(cfg.ckpt_dir)) else script_path / cfg.ckpt_dir
         ckpt_dir.mkdir(exist_ok=True)

@@ -236,6 +236,48 @@ _SIGNATURES = {
     'stof_kuleshov_workspace_bytes': (_c.c_size_t, [_c.POINTER(KuleshovDesc), _c.c_int64]),
     'stof_kuleshov_forward': (_c.c_int, [_c.POINTER(KuleshovDesc), _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
                                          _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    'stof_kuleshov_dropout_keep': (_c.c_int, [_c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_int32, _c.c_int64, _c.c_int64, _c.c_double,
+                                              _c.c_void_p]),
+    'stof_kuleshov_train_constants': (_c.c_int, [_c.POINTER(_c.c_int64)]),
+    'stof_kuleshov_train_frag_floats': (_c.c_size_t, [_c.c_int32] * 4),
+    'stof_kuleshov_train_pack_frag': (_c.c_int, [_c.c_void_p] + [_c.c_int32] * 4 + [_c.c_void_p] * 2),
+    'stof_kuleshov_train_pack_final': (_c.c_int, [_c.c_void_p] * 3),
+    'stof_kuleshov_train_fc_frag_floats': (_c.c_size_t, [_c.POINTER(KuleshovDesc)]),
+    'stof_kuleshov_train_pack_fc': (_c.c_int, [_c.POINTER(KuleshovDesc)] + [_c.c_void_p] * 3),
+    'stof_kuleshov_train_down0': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64] + [_c.c_void_p] * 4),
+    'stof_kuleshov_train_conv': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64] + [_c.c_int32] * 4 + [_c.c_void_p] * 2 +
+                                 [_c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p]),
+    'stof_kuleshov_train_stats_workspace_bytes': (_c.c_size_t, []),
+    'stof_kuleshov_train_stats': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int32] + [_c.c_void_p] * 4 + [_c.c_double] * 2 +
+                                  [_c.c_void_p] * 4 + [_c.c_size_t, _c.c_void_p]),
+    'stof_kuleshov_train_apply_down': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_void_p, _c.c_int64,
+                                                  _c.c_void_p]),
+    'stof_kuleshov_train_apply_up': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_void_p, _c.c_uint64, _c.c_uint32,
+                                                _c.c_uint32, _c.c_int32, _c.c_double, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    'stof_kuleshov_train_apply_bott': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_double,
+                                                  _c.c_void_p, _c.c_void_p]),
+    'stof_kuleshov_train_tail': (_c.c_int, [_c.POINTER(KuleshovDesc), _c.c_void_p, _c.c_int64] + [_c.c_void_p] * 7),
+    'stof_kuleshov_train_fc_bwd': (_c.c_int, [_c.POINTER(KuleshovDesc)] + [_c.c_void_p] * 3 + [_c.c_int64] + [_c.c_void_p] * 4),
+    'stof_kuleshov_train_final_bwd_workspace_bytes': (_c.c_size_t, []),
+    'stof_kuleshov_train_final_bwd': (_c.c_int, [_c.POINTER(KuleshovDesc)] + [_c.c_void_p] * 3 + [_c.c_int64] + [_c.c_void_p] * 4 +
+                                      [_c.c_size_t, _c.c_void_p]),
+    'stof_kuleshov_train_gather_up': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int32, _c.c_uint64, _c.c_uint32,
+                                                 _c.c_uint32, _c.c_int32, _c.c_double, _c.c_void_p, _c.c_void_p]),
+    'stof_kuleshov_train_gather_down': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64,
+                                                   _c.c_int32, _c.c_void_p, _c.c_void_p]),
+    'stof_kuleshov_train_gather_bott': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_uint64, _c.c_uint32, _c.c_uint32,
+                                                   _c.c_double, _c.c_void_p, _c.c_void_p]),
+    'stof_kuleshov_train_bn_bwd': (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int64, _c.c_int32, _c.c_int32] + [_c.c_void_p] * 4 +
+                                   [_c.c_size_t, _c.c_void_p]),
+    'stof_kuleshov_train_wgrad_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int64] + [_c.c_int32] * 3),
+    'stof_kuleshov_train_wgrad': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int64] + [_c.c_int32] * 4 +
+                                  [_c.c_void_p] * 3 + [_c.c_size_t, _c.c_void_p]),
+    'stof_kuleshov_train_dgrad_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int64] + [_c.c_int32] * 3),
+    'stof_kuleshov_train_dgrad': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64] + [_c.c_int32] * 4 + [_c.c_void_p] * 2 + [_c.c_int64] +
+                                  [_c.c_void_p] * 2 + [_c.c_size_t, _c.c_void_p]),
+    'stof_kuleshov_train_down0_bwd_workspace_bytes': (_c.c_size_t, []),
+    'stof_kuleshov_train_down0_bwd': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64] +
+                                      [_c.c_void_p] * 3 + [_c.c_int64, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     'stof_iq2rf': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_double, _c.c_double, _c.c_double,
                               _c.c_int32, _c.c_void_p]),
     'stof_augment': (_c.c_int, [_c.POINTER(AugmentDesc), _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p,

@@ -6,6 +6,9 @@ strict=True (`down_conv{i}`, `down_bn{i}`, `bottleneck`, `up_conv{i}`, `up_bn{i}
 
   forward_aten(x)     the reference's forward (crop included) on stock ATen layers; it trains, and in train mode the
                       Dropouts are live and BatchNorm uses batch statistics and updates its running ones;
+  forward_train_kernels(x)  a train-mode call on the gfx950 training kernels (kuleshov_training.py), taken by `forward` when
+                      `train_route = 'kernels'` (the class default is 'aten'): batch statistics, Dropout masks that are a pure
+                      function of (`dropout_seed`, `dropout_call`), the full backward pass in exact fp32;
   forward_kernels(x)  inference on the gfx950 kernels of csrc/kuleshov.hip in exact fp32: a vector kernel for down_conv0,
                       one implicit-GEMM kernel for the nine 128 .. 1024-wide convolutions (stride 1 or 2; BatchNorm and
                       both leaky ReLUs in the epilogue; the pixel shuffle is the store address of the up convolutions and
@@ -66,7 +69,10 @@ class Kuleshov(_KernelRoute, nn.Module):
     128 -> 2 convolution whose flattened output feeds Linear(fc_dim, output_length)."""
     max_workspace_bytes = 512 << 20
     _KERNEL_CONFIG = 'rows of at least input_length samples with one eps in every BatchNorm'
-    _EVAL_ONLY = True
+    _EVAL_ONLY = True       # the inference kernels serve eval mode only; train mode is decided by `train_route`
+    train_route = 'aten'    # 'aten' | 'kernels': what a train-mode call runs on
+    dropout_seed = None     # seed of the kernel route's Dropout masks; None: torch.initial_seed() at first use
+    dropout_call = 0        # counts the kernel route's train-mode forwards: the `call` word of the masks' counter
     tile_variant = 0            # 0: wave tile chosen per layer; 1, 2, 3 pin it (bitwise the same; for tests and timing)
 
     def __init__(self, input_length=None, output_length=None, num_layers=4):
@@ -185,3 +191,51 @@ class Kuleshov(_KernelRoute, nn.Module):
         x = self.final_conv(x)                                   # [N, 2, F]
         x = x.transpose(1, 2).reshape(x.size(0), 2 * x.size(2))  # SubPixel1D + view: flat[n, 2 pos + ch]
         return self.output_fc(x).unsqueeze(1)
+
+    def forward_train_kernels(self, x):
+        """y [N, 1, output_length] float32 of a train-mode call on the gfx950 training kernels (kuleshov_training.py), with an
+        autograd graph when one is recorded: its backward fills the gradient of every parameter (and of x, if it asks for one)
+        in exact fp32.  BatchNorm uses batch statistics and the running statistics are updated, also under no_grad; the
+        Dropout masks are a pure function of (`dropout_seed`, `dropout_call`, rank, site, row, element), and `dropout_call`
+        moves on by one.  Raises where the kernels do not apply.  Not chunked by `max_workspace_bytes`: the batch statistics
+        and the backward need every stage output of the whole batch."""
+        from ._train_boundary import commit_running_stats, train_engine
+        from .kuleshov_training import SITES, KuleshovFunction, KuleshovTrainEngine
+        if not self.training:
+            raise NotImplementedError("Kuleshov: train_route='kernels' serves train mode only (batch statistics, Dropout); "
+                                      'eval-mode calls take the inference kernels or forward_aten')
+        self._check_kernels(x)
+        N = int(x.shape[0])
+        u0 = chain_lengths(self.input_length)['up'][0]
+        if N * u0 == 1:                                     # torch's BatchNorm check, word for word, before anything is touched
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size {torch.Size([N, 1024, u0])}')
+        ps = [float(getattr(self, name).p) for name in SITES]
+        for name, p in zip(SITES, ps):
+            if not 0.0 <= p < 1.0:
+                raise ValueError(f'Kuleshov: the gfx950 kernels need a Dropout p in [0, 1) (got {name}.p = {p})')
+        bns = self._batch_norms()
+        if any(bn.momentum is None or not bn.track_running_stats or not bn.affine for bn in bns):
+            raise NotImplementedError('Kuleshov: the gfx950 training kernels need affine BatchNorm layers with a momentum and '
+                                      'running statistics')
+        if self.dropout_seed is None:
+            self.dropout_seed = int(torch.initial_seed())
+        engine = train_engine(self, str(x.device), lambda: KuleshovTrainEngine(x.device, self.input_length, self.output_length))
+        engine.eps = float(bns[0].eps)
+        engine.momentum = [float(bn.momentum) for bn in bns]
+        engine.running = [(bn.running_mean, bn.running_var) for bn in bns]
+        engine.seed, engine.call, engine.p = int(self.dropout_seed), int(self.dropout_call), ps
+        engine.rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
+        names, params = zip(*self.named_parameters())
+        y = KuleshovFunction.apply(x, engine, names, *params)
+        if N:
+            commit_running_stats(bns, engine.new_running)
+        self.dropout_call = int(self.dropout_call) + 1
+        return y
+
+    def forward(self, x):
+        route = self.train_route
+        if route not in ('aten', 'kernels'):
+            raise ValueError(f"Kuleshov.train_route must be 'aten' or 'kernels' (got {route!r})")
+        if route == 'kernels' and self.training:
+            return self.forward_train_kernels(x)
+        return super().forward(x)
