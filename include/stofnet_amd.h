@@ -328,6 +328,61 @@ int stof_augment_uniforms(uint64_t seed, uint32_t rank, uint32_t call, int32_t s
                           void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Plane-wave delay-and-sum beamformer (utils/beamform.py: bf_das, bf_das_rx) for a batch of frames.
+ *
+ * sig[F][A][S][Ne] (frames, transmit angles, samples, elements; element fastest) in one of four dtypes; complex values
+ * are interleaved (re, im).  Pixels are a LIST of P points (x[p], z[p]) in any order.  Per frame f, angle a, pixel p and
+ * element k, all in double:
+ *     drx = hypot(x - xe[k], z),  tau = (dtx[a][p] + drx) / c,  i = (tau - t0) * fs,  fl = floor(i)
+ *     the term counts iff |x - xe[k]| < z / fnumber / 2 (strict) and 1 <= i <= S - 1 (NaN and +-inf fail both):
+ *     term = sig[f][a][fl][k] * (fl + 1 - i) + sig[f][a][fl + 1][k] * (i - fl)
+ *     (at i == S - 1 the second weight is 0 and row S is not read: no input value leads to a read outside sig);
+ *     complex dtypes with rotate[f][a][k] != 0: term *= exp(2 pi i f0 tau), f0 tau reduced to [0, 1) cycles in double.
+ * The terms of one (f, a, p) are added in accumulators of sig's scalar type starting at 0, in a fixed order: the host entry
+ * for k ascending; the kernel as eight partial sums (k = g mod 8, ascending) combined pairwise (g ^ 1, g ^ 2, g ^ 4).
+ * compound != 0: out[f][p] = the angle sums added for a ascending; compound == 0: out[f][a][p] = the angle sum.  No atomics:
+ * a frame's result is bitwise independent of F and of its place in the batch.
+ * rotate[F][A][Ne] (bytes; read for complex dtypes only): the reference rotates a channel iff any value it gathered from
+ * it is not purely real; callers set the byte iff column sig[f][a][:, k] has a non-zero imaginary part anywhere.
+ *
+ * dtx[A][P] comes from stof_das_tx_distance (host, libm): W = xe[Ne - 1] - xe[0], beta = 1e-8,
+ *     v = (-W cos(t) sin(t) / beta, -W cos(t)^2 / beta),  g = |v0| - W/2 if |v0| > W/2 else 0,
+ *     dtx = hypot(x - v0, z - v1) - hypot(g, v1)
+ * -- a difference of two numbers near 1e6 m, so every consumer has to read the same doubles.
+ *
+ * stof_das_beamform_host: the same arithmetic (one shared header) in plain loops on host pointers; no GPU needed.
+ * stof_das_beamform: sig, x, z, dtx, xe, rotate, out are device pointers; one launch on `stream`.
+ * stof_das_bmode: img[F][n] of `dtype` -> bmode[F][n] of its real type (float for F32 / C64, else double):
+ *     20 log10 |img|; pixels whose value is not finite (magnitude 0, NaN or inf) take the smallest finite value of their
+ *     frame; the frame's maximum is subtracted.  A frame without any finite value gives zeros.  Two launches on `stream`, no
+ *     host read; workspace: stof_das_workspace_bytes(F, n) bytes of device memory (block partials of the fixed-tree min / max).
+ * Errors: NULL desc / bad dtype / negative sizes / a missing pointer -> STOF_ERR_BAD_ARG; more than 262140 frames (bmode:
+ * 65535) or 2^39 pixels -> STOF_ERR_UNSUPPORTED; a short workspace -> STOF_ERR_WORKSPACE.  F, P or n == 0 -> STOF_OK without
+ * work; A == 0 or Ne == 0 -> zeros.
+ * ------------------------------------------------------------------------- */
+#define STOF_DAS_F32 0
+#define STOF_DAS_F64 1
+#define STOF_DAS_C64 2
+#define STOF_DAS_C128 3
+typedef struct stof_das_desc {
+    double c, t0, fs, f0;        /* speed of sound, time of sample 0, sampling and demodulation frequency */
+    double fnumber;              /* receive cone: |x - xe| < z / fnumber / 2                              */
+    int32_t dtype;               /* STOF_DAS_*                                                            */
+    int32_t compound;            /* != 0: sum the angles                                                  */
+} stof_das_desc;
+int stof_das_tx_distance(const double* xe, int64_t Ne, const double* angles, int64_t A, const double* x, const double* z,
+                         int64_t P, double* dtx);
+int stof_das_beamform_host(const stof_das_desc* desc, const void* sig, int64_t F, int64_t A, int64_t S, int64_t Ne,
+                           const double* x, const double* z, const double* dtx, int64_t P, const double* xe,
+                           const uint8_t* rotate, void* out);
+int stof_das_beamform(const stof_das_desc* desc, const void* sig, int64_t F, int64_t A, int64_t S, int64_t Ne,
+                      const double* x, const double* z, const double* dtx, int64_t P, const double* xe,
+                      const uint8_t* rotate, void* out, void* stream);
+size_t stof_das_workspace_bytes(int64_t F, int64_t n);
+int stof_das_bmode(int32_t dtype, const void* img, int64_t F, int64_t n, void* bmode, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Zonzini baselines (models/zonzini.py: ZonziniNetSmall / ZonziniNetLarge), inference in exact fp32.
  * ------------------------------------------------------------------------- */
 #define STOF_ZONZINI_SMALL 0      /* Conv1d 1->16->32->64->64, fc1 64->1024;   rows need L >= 936   */

@@ -69,6 +69,14 @@ class AugmentDesc(ctypes.Structure):
                 ('call', ctypes.c_uint32)]
 
 
+class DasDesc(ctypes.Structure):
+    _fields_ = [('c', ctypes.c_double), ('t0', ctypes.c_double), ('fs', ctypes.c_double), ('f0', ctypes.c_double),
+                ('fnumber', ctypes.c_double), ('dtype', ctypes.c_int32), ('compound', ctypes.c_int32)]
+
+
+DAS_F32, DAS_F64, DAS_C64, DAS_C128 = 0, 1, 2, 3
+
+
 class StofnetLibraryMissing(ImportError):
     pass
 
@@ -284,6 +292,14 @@ _SIGNATURES = {
                                 _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     'stof_augment_uniforms': (_c.c_int, [_c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64,
                                          _c.c_void_p]),
+    'stof_das_tx_distance': (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64,
+                                        _c.c_void_p]),
+    'stof_das_beamform_host': (_c.c_int, [_c.POINTER(DasDesc), _c.c_void_p] + [_c.c_int64] * 4 + [_c.c_void_p] * 3 + [_c.c_int64] +
+                               [_c.c_void_p] * 3),
+    'stof_das_beamform': (_c.c_int, [_c.POINTER(DasDesc), _c.c_void_p] + [_c.c_int64] * 4 + [_c.c_void_p] * 3 + [_c.c_int64] +
+                          [_c.c_void_p] * 4),
+    'stof_das_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int64]),
+    'stof_das_bmode': (_c.c_int, [_c.c_int32, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     'stof_toa_rmse': (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_float,
                                  _c.c_void_p, _c.c_void_p]),
     'stof_train_repack_floats': (_c.c_size_t, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32]),

@@ -15,11 +15,13 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libstofnet_amd.so')
-SOURCES = ['pack_weights.cpp', 'convstack.hip', 'sgb_expand.hip', 'shuffle_picker.hip', 'hilbert.hip', 'gradpeak.hip', 'gradpeak_f64.hip', 'neighbors.hip', 'train.hip', 'widths.hip', 'edsr_train.hip', 'espcn_train.hip', 'zonzini.hip', 'zonzini_train.hip', 'sincnet.hip', 'sincnet_train.hip', 'riders.hip', 'augment.hip', 'waveunet.hip', 'waveunet_train.hip', 'kuleshov.hip', 'kuleshov_train.hip']
+SOURCES = ['pack_weights.cpp', 'convstack.hip', 'sgb_expand.hip', 'shuffle_picker.hip', 'hilbert.hip', 'gradpeak.hip', 'gradpeak_f64.hip', 'neighbors.hip', 'train.hip', 'widths.hip', 'edsr_train.hip', 'espcn_train.hip', 'zonzini.hip', 'zonzini_train.hip', 'sincnet.hip', 'sincnet_train.hip', 'riders.hip', 'augment.hip', 'waveunet.hip', 'waveunet_train.hip', 'kuleshov.hip', 'kuleshov_train.hip', 'beamform.hip']
 ARCH = 'gfx950'
 # convstack.hip: the SLP vectoriser pairs scalar fp32 FMAs into v_pk_fma_f32 (slow beside MFMAs) and thereby defeats the
 # v_fma_mix_f32 selection of the sweep's epilogue (see mix_add in convstack.hip)
-EXTRA_FLAGS = {'convstack.hip': ['-fno-slp-vectorize']}
+# beamform.hip: no fused multiply-adds, so that the host entry, every kernel instantiation and every batch size round a frame's
+# terms alike (a frame's result is bitwise independent of the batch it sits in)
+EXTRA_FLAGS = {'convstack.hip': ['-fno-slp-vectorize'], 'beamform.hip': ['-ffp-contract=off']}
 
 
 def _hipcc() -> str:
