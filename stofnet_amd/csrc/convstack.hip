@@ -1525,9 +1525,9 @@ int launch_forward(const stof_net_desc* desc, const void* packed_dev, const floa
     const float* ew = base + off;      off += 5ull * NF_SGB * NF;
     const float* ebias = base + off;
 
-    // split fp16: two-pass tile-major layers (body_p2.h) unless STOF_BODY_P2=0 (the r3 chunk-major kernel alone, for A/B runs);
-    // waveforms shorter than 2 S stream rows go to the r3 kernel either way (body_p2_rows_ok)
-    static const bool body_p2 = PREC == STOF_PREC_F16X3 && body_p2_enabled();
+    // split fp16: two-pass tile-major layers (body_p2.h); waveforms shorter than 2 S stream rows go to the r3 chunk-major kernel
+    // (body_p2_rows_ok), which is also the fp32 sweep
+    constexpr bool body_p2 = PREC == STOF_PREC_F16X3;
     constexpr int RF = PREC == STOF_PREC_F16X3 ? ROWF16 : ROWF;
     using Lds = BodyLds<BODY_S, BODY_RING, BODY_RAWRING, RF>;
     const size_t body_p2_bytes = Lds::BYTES + BODY_P2_C1F * sizeof(float);
@@ -1888,12 +1888,9 @@ static int train_sweep_impl(const stof_net_desc* desc, const void* blob_dev, con
     if ((L + GAP) * N > 0x7fffffffLL || N * L * NF > 0x7fffffffffLL) return STOF_ERR_UNSUPPORTED;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     using Lds16 = BodyLds<BODY_S, BODY_RING, BODY_RAWRING, ROWF16>;
-    static const bool p2 = body_p2_enabled();
-    if (split && !p2) return STOF_ERR_UNSUPPORTED;              // split-row dumps exist in the two-pass kernel only
     auto kernel = split ? &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, false, true>
-                  : p2  ? &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, false>
-                        : &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, true, false>;
-    const size_t lds_bytes = Lds16::BYTES + (p2 ? BODY_P2_C1F * sizeof(float) : 0);
+                        : &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, false>;
+    const size_t lds_bytes = Lds16::BYTES + BODY_P2_C1F * sizeof(float);
     static LdsLimitOnce lds[2];
     if (int st = lds[split ? 1 : 0].ensure(reinterpret_cast<const void*>(kernel), (int)lds_bytes)) return st;
     const float* base = static_cast<const float*>(blob_dev);
@@ -1911,7 +1908,7 @@ static int train_sweep_impl(const stof_net_desc* desc, const void* blob_dev, con
 #endif
     int64_t wgs = 0;
     if (int st = train_sweep_geometry(desc, bp, N, L, &wgs)) return st;
-    if (p2 && !body_p2_rows_ok(bp.seg_len, bp.halo)) {            // short waveforms: the r3 kernel (fp32 dumps only)
+    if (!body_p2_rows_ok(bp.seg_len, bp.halo)) {                  // short waveforms: the r3 kernel (fp32 dumps only)
         if (split) return STOF_ERR_UNSUPPORTED;
         auto k3 = &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, true, false>;
         static LdsLimitOnce lds3;
@@ -2037,12 +2034,9 @@ static int train_sweep_bwd_impl(const stof_net_desc* desc, const void* blob_dev,
     if ((L + GAP) * N > 0x7fffffffLL || N * L * NF > 0x7fffffffffLL) return STOF_ERR_UNSUPPORTED;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     using Lds16 = BodyLds<BODY_S, BODY_RING, BODY_RAWRING, ROWF16>;
-    static const bool p2 = body_p2_enabled();
-    if (split && !p2) return STOF_ERR_UNSUPPORTED;
     auto kernel = split ? &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, true, true>
-                  : p2  ? &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, true>
-                        : &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, true, true>;
-    const size_t lds_bytes = Lds16::BYTES + (p2 ? BODY_P2_C1F * sizeof(float) : 0);
+                        : &body_sweep_p2_kernel<BODY_S, BODY_RING, BODY_RAWRING, true, true>;
+    const size_t lds_bytes = Lds16::BYTES + BODY_P2_C1F * sizeof(float);
     static LdsLimitOnce lds[2];
     if (int st = lds[split ? 1 : 0].ensure(reinterpret_cast<const void*>(kernel), (int)lds_bytes)) return st;
     const float* base = static_cast<const float*>(blob_dev);
@@ -2059,7 +2053,7 @@ static int train_sweep_bwd_impl(const stof_net_desc* desc, const void* blob_dev,
 #endif
     int64_t wgs = 0;
     if (int st = train_sweep_geometry(desc, bp, N, L, &wgs)) return st;
-    if (p2 && !body_p2_rows_ok(bp.seg_len, bp.halo)) {            // short waveforms: the r3 kernel (fp32 dumps only)
+    if (!body_p2_rows_ok(bp.seg_len, bp.halo)) {                  // short waveforms: the r3 kernel (fp32 dumps only)
         if (split) return STOF_ERR_UNSUPPORTED;
         auto k3 = &body_sweep_kernel<STOF_PREC_F16X3, BODY_S, BODY_RING, BODY_RAWRING, true, true>;
         static LdsLimitOnce lds3;

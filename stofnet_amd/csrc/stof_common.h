@@ -66,12 +66,6 @@ constexpr uint32_t PACK_MAGIC = 0x464F5453u;
 // 16x16x32 body: output channel held by row i (0..15) of M-tile m (0, 1) of the 32-channel block `block`:
 // accumulator element e of lane (col, q) is row 4q + e, i.e. channel 32 block + 8q + 4m + e.
 constexpr int body16_out_channel(int block, int m, int i) { return 32 * block + 8 * (i >> 2) + 4 * m + (i & 3); }
-// r4: the 16x16x32 body sweeps its k7 layers two-pass tile-major (body_p2.h); STOF_BODY_P2=0 selects the r3 chunk-major kernel
-// on the same packed blob (A/B runs)
-inline bool body_p2_enabled() {
-    const char* e = getenv("STOF_BODY_P2");
-    return e == nullptr || e[0] != '0';
-}
 constexpr int LAST16_F = 6 * 2 * 64 * 4;      // floats of the off_last16 section
 
 }  // namespace stof

@@ -156,6 +156,7 @@ class TrainEngine(LayerKernels):
     # Two routes, fixed per engine by `self.sweep`: the fused sweeps (body forward and backward as one launch each plus one
     # batched weight-gradient launch) or layer by layer.  Within the sweep route the forward sweep decides whether the dumps
     # are split rows (`SavedForward.split`) and the backward follows it.
+    split_dumps = True          # False: the forward sweep writes fp32 dumps whatever the shape
 
     def __init__(self, dev, r, sgb, precision='fp32', scale=80, num_blocks=13, body_kernel=7, num_features=64, in_channels=1):
         if precision not in ('fp32', 'f16x3'):
@@ -257,8 +258,8 @@ class TrainEngine(LayerKernels):
         z = torch.empty((n, L * r), dtype=torch.float32, device=self.dev)
         # Dumps a backward will read are SPLIT ROWS ([64 x fp16 hi | 64 x fp16 lo] per 256-byte row: the halves the sweeps
         # compute anyway; the batched weight-gradient kernel stages them without converting) wherever stof_train_sweep_split
-        # takes the shape; fp32 dumps otherwise, and everywhere under STOF_TRAIN_SPLIT_DUMPS=0 (route comparisons).
-        s.split = keep and os.environ.get('STOF_TRAIN_SPLIT_DUMPS', '1') != '0'
+        # takes the shape; fp32 dumps otherwise, and everywhere with `split_dumps = False` (tests compare the two).
+        s.split = keep and self.split_dumps
         sweep_args = (ctypes.byref(desc), _lib.ptr(blob), _lib.ptr(s.x), _lib.ptr(s.e), _lib.ptr(dump), _lib.ptr(z), n, L, st)
         if s.split:
             code = lib.stof_train_sweep_split(*sweep_args)

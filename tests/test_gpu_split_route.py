@@ -6,13 +6,13 @@ On a 256-CU device every other training test lands on the r3 sweep kernel with f
 
   * the small split-row kernels bit for bit (stof_train_to_split_rows, stof_train_add_split / _split2,
     stof_train_conv_last_dgrad_split) and their return codes;
-  * stof_train_wgrad_batch_split in every kernel form (STOF_TRAIN_WGRAD_ASYNC unset, '3', '1', '2', '0', mixed split bits, and
-    stof_train_wgrad_batch) where a work-group takes a second tile: dyadic operands bitwise, Gaussian operands at
-    max(2e-6, 4 x e32);
+  * stof_train_wgrad_batch_split on both of its kernels (every operand split: conv_wgrad_split_async16_kernel; mixed split
+    bits and stof_train_wgrad_batch: the register-staged conv_wgrad_f16x3_batch_kernel) where a work-group takes a second
+    tile: dyadic operands bitwise, Gaussian operands at max(2e-6, 4 x e32);
   * stof_train_sweep / _split and stof_train_sweep_bwd / _split through the C ABI with stof_net_desc.seg_policy forcing the
     geometry, every dump tensor against its float64 stage reference computed from the kernel's OWN previous tensor at 2e-6 x
     max|ref|, next to the layer kernel (stof_train_conv, f16x3) on the same operands;
-  * the whole step where the engine itself picks the split route, against float64 autograd, and its route switches.
+  * the whole step where the engine itself picks the split route, against float64 autograd, and the same step on fp32 dumps.
 
 Figures go to profiles/split_route.jsonl.  The float64 references are matmuls / autograd on the device; they never touch the
 kernels under test."""
@@ -35,7 +35,6 @@ PROFILE = os.path.join(ROOT, 'profiles', 'split_route.jsonl')
 BOUND = sr.STAGE_BOUND
 OUT_SCALE = 0.25
 CANARY_FLOATS = 4096
-ENV_ASYNC, ENV_DUMPS = 'STOF_TRAIN_WGRAD_ASYNC', 'STOF_TRAIN_SPLIT_DUMPS'
 
 
 @pytest.fixture(scope='module')
@@ -190,9 +189,6 @@ def test_small_split_kernels_return_codes(lib, dev):
 
 
 # ------------------------------------------------------------------------------------------ stof_train_wgrad_batch_split
-FORMS = [None, '3', '1', '2', '0']
-
-
 def _ptrs(ts):
     from stofnet_amd import _lib
     return (ctypes.c_void_p * len(ts))(*[_lib.ptr(t) for t in ts])
@@ -202,18 +198,11 @@ def _batch_groups(lib, count):
     return sr.wgrad_batch_groups(lib.stof_train_wgrad_batch_workspace_bytes(count, 7), count)
 
 
-def _set_form(monkeypatch, form):
-    if form is None:
-        monkeypatch.delenv(ENV_ASYNC, raising=False)
-    else:
-        monkeypatch.setenv(ENV_ASYNC, form)
-
-
 _batch_cache = {}
 
 
 def _batch_case(lib, dev, count, which, mode):
-    """operands (fp32 and split rows) and the float64 reference of one (count, shape, kind of operand), shared by the forms"""
+    """operands (fp32 and split rows) and the float64 reference of one (count, shape, kind of operand), shared by the tests"""
     key = (count, which, mode)
     if key not in _batch_cache:
         _batch_cache.clear()
@@ -276,37 +265,28 @@ def _assert_exact(c, count, got, out_scale, what):
         assert torch.equal(got[1][i], mt.exact_fp32(out_scale * c['db'][i])), (what, i, 'db')
 
 
-@pytest.mark.parametrize('form', FORMS)
 @pytest.mark.parametrize('which', ['short', 'long'])
 @pytest.mark.parametrize('count', [11, 3])
-def test_wgrad_batch_split_second_tile_exact(lib, dev, monkeypatch, count, which, form):
-    """Every operand split, dyadic (lo = 0): dw and db of every layer bitwise equal to the float64 reference, in each kernel form
-    -- unset / '3' conv_wgrad_split_async16_kernel, '1' conv_wgrad_split_async_kernel<7, 1>, '2' <7, 2> (eight waves: G / 2
-    work-groups, so an odd G falls through to the register-staged kernel by design; G = 2 CUs / count is 46 at count 11 and
-    170 at count 3 on a 256-CU device, both even: both counts run the eight-wave kernel there, which the assertion below
-    states for the device at hand), '0' the register-staged kernel on split operands.  One dropped, doubled or stale tile, one
-    wrong swizzle slot or tap offset fails it.
-    What this cannot show: WHICH kernel a form ran.  On dyadic operands every kernel, a silent fall-through to the register-staged
-    one included, gives the same bits; that '1', '2' and '3' reach their kernels is read off the dispatch in
-    wgrad_batch_impl (train.hip), not observed.  Indirect evidence only: forms that sum in different orders differ on Gaussian
-    operands (profiles/split_route.jsonl: '2' and '3' differ from '0' / '1', which agree), and breaking the copy of
-    conv_wgrad_split_async16_kernel alone failed exactly the unset / '3' cases."""
+def test_wgrad_batch_split_second_tile_exact(lib, dev, count, which):
+    """Every operand split, dyadic (lo = 0), K = 7: the one case wgrad_batch_impl (train.hip) sends to
+    conv_wgrad_split_async16_kernel.  dw and db of every layer bitwise equal to the float64 reference, at a layer count that
+    gives few groups many tiles (11: G = 46 on a 256-CU device) and one that gives many groups few (3: G = 170).  One dropped,
+    doubled or stale tile, one wrong swizzle slot or tap offset fails it.
+    What this cannot show: WHICH kernel ran.  On dyadic operands the register-staged kernel gives the same bits; that all-split
+    operands reach the global_load_lds kernel is read off the dispatch, not observed.  Indirect evidence only: breaking the copy
+    of conv_wgrad_split_async16_kernel alone failed exactly these cases."""
     c = _batch_case(lib, dev, count, which, 'dyadic')
-    if form == '2':
-        print(f'count {count}: G = {c["G"]}, the eight-wave kernel {"runs" if c["G"] % 2 == 0 else "is NOT reached (odd G)"}')
-        assert any(_batch_groups(lib, n) % 2 == 0 for n in (11, 3))
-    _set_form(monkeypatch, form)
     bits = (1 << count) - 1
-    _assert_exact(c, count, _run_batch(lib, dev, c, count, bits, bits, OUT_SCALE), OUT_SCALE, (count, which, form))
+    _assert_exact(c, count, _run_batch(lib, dev, c, count, bits, bits, OUT_SCALE), OUT_SCALE, (count, which))
 
 
 @pytest.mark.parametrize('which', ['short', 'long'])
 @pytest.mark.parametrize('count', [11, 3])
-def test_wgrad_batch_mixed_operands_exact(lib, dev, monkeypatch, count, which):
-    """The register-staged kernel with mixed split bits (x split and dy fp32, the reverse, alternating layers),
-    stof_train_wgrad_batch on fp32 operands, and out_scale = 2^-10 (a power of two: still bitwise)."""
+def test_wgrad_batch_mixed_operands_exact(lib, dev, count, which):
+    """conv_wgrad_f16x3_batch_kernel, which every batch with one operand that is not split reaches, and its split staging: x
+    split and dy fp32, the reverse, alternating layers; then fp32 operands through both entry points.  The last line is all
+    split again (conv_wgrad_split_async16_kernel) at out_scale = 2^-10 (a power of two: still bitwise)."""
     c = _batch_case(lib, dev, count, which, 'dyadic')
-    monkeypatch.delenv(ENV_ASYNC, raising=False)
     bits = (1 << count) - 1
     alt = 0x555 & bits
     for xb, db_ in ((bits, 0), (0, bits), (alt, bits ^ alt), (0, 0)):
@@ -315,13 +295,12 @@ def test_wgrad_batch_mixed_operands_exact(lib, dev, monkeypatch, count, which):
     _assert_exact(c, count, _run_batch(lib, dev, c, count, bits, bits, 2.0 ** -10), 2.0 ** -10, (count, which, 'scale'))
 
 
-@pytest.mark.parametrize('form', FORMS)
 @pytest.mark.parametrize('count', [11, 3])
-def test_wgrad_batch_split_second_tile_gaussian(lib, dev, monkeypatch, count, form):
-    """Gaussian operands split with a non-zero lo, at the long shape: rel(dw), rel(db) <= max(2e-6, 4 x e32), e32 the deviation
-    from float64 of the same gradient evaluated by torch in fp32 (the rule and margin of test_gpu_multi_tile)."""
+def test_wgrad_batch_split_second_tile_gaussian(lib, dev, count):
+    """conv_wgrad_split_async16_kernel (every operand split) on Gaussian operands with a non-zero lo, at the long shape, so that
+    the lo halves and the hi*lo / lo*hi products count: rel(dw), rel(db) <= max(2e-6, 4 x e32), e32 the deviation from float64
+    of the same gradient evaluated by torch in fp32 (the rule and margin of test_gpu_multi_tile)."""
     c = _batch_case(lib, dev, count, 'long', 'gauss')
-    _set_form(monkeypatch, form)
     bits = (1 << count) - 1
     dw, db = _run_batch(lib, dev, c, count, bits, bits, OUT_SCALE)
     worst = {}
@@ -329,11 +308,11 @@ def test_wgrad_batch_split_second_tile_gaussian(lib, dev, monkeypatch, count, fo
         err = max(sr.rel(got[i], OUT_SCALE * c[tag][i]) for i in range(count))
         e32 = max(sr.rel(c['e32'][i][k], c[tag][i]) for i in range(count))
         worst[tag] = (err, max(2e-6, 4 * e32), e32)
-    _record({f'wgrad_batch_split count {count} form {form or "unset"}': {
+    _record({f'wgrad_batch_split count {count}': {
         'rows': c['N'] * c['L'], 'G': c['G'],
         **{t: {'kernel': _rounded(v[0]), 'e32': _rounded(v[2]), 'bound': _rounded(v[1])} for t, v in worst.items()}}})
     for tag, (err, bound, _) in worst.items():
-        assert err <= bound, (count, form, tag, err, bound)
+        assert err <= bound, (count, tag, err, bound)
 
 
 def test_wgrad_batch_split_return_codes(lib, dev):
@@ -761,15 +740,11 @@ def test_whole_step_on_the_split_route(dev, cus, monkeypatch, shape):
     (SavedForward.split and .sweep).  Against float64 autograd of the same network on the device (sr.network_forward and
     sr.loss_ref: matmuls, so that float64 runs on the device; pinned against oracle/'s forward and loss on the CPU, with one
     and with three pooling windows): loss 2e-6, predictions 1e-5,
-    every parameter gradient 2e-3 x max|grad| (the f16x3 bar of DESIGN.md section 8).  Twice: bitwise.  Then the route switches:
-    STOF_TRAIN_WGRAD_ASYNC '1', '2', '0' stay on split dumps, STOF_TRAIN_SPLIT_DUMPS '0' leaves them.  '0' (register-staged) and
-    '1' (four waves, 32x32x16) walk the same tiles per partial and the same K-steps per tile: bitwise equal .weight gradients;
-    the default '3' (16x16x32: 32 time rows per MFMA) and '2' (eight waves, two K-halves per tile) group a tile's rows
-    differently: 1e-5 x max; fp32 dumps: 2e-4 x max|grad|."""
+    every parameter gradient 2e-3 x max|grad| (the f16x3 bar of DESIGN.md section 8).  Twice: bitwise.  Then one more step with
+    `split_dumps = False`: the engine stays on the sweeps and leaves split rows (fp32 dumps, hence the register-staged
+    weight-gradient kernel), and every gradient agrees with the split route's at 2e-4 x max|grad|."""
     from oracle.pickers_oracle import gaussian_kernel
     N, L, r = (cus, 380, 4) if shape == 'cu_x_380' else (1, 20000, 10)
-    for k in (ENV_ASYNC, ENV_DUMPS):
-        monkeypatch.delenv(k, raising=False)
     sd, tr = _make(dev, r, 80, seed=3008)
     frame = torch.from_numpy(synth.synth_echo(N, L, seed=41)).to(dev)
     rng = np.random.default_rng(5)
@@ -808,17 +783,9 @@ def test_whole_step_on_the_split_route(dev, cus, monkeypatch, shape):
     # (the loss value is a float64 atomicAdd over work-groups, loss_grad_kernel: its last bit moves between runs; no gradient reads it)
     assert abs(loss2 - loss) <= 1e-12 * abs(loss) and torch.equal(pred2, pred)
     assert all(torch.equal(grads2[n], grads[n]) for n in grads)
-    got = {'3': grads}
-    for env, value, split in ((ENV_ASYNC, '1', True), (ENV_ASYNC, '2', True), (ENV_ASYNC, '0', True), (ENV_DUMPS, '0', False)):
-        for k in (ENV_ASYNC, ENV_DUMPS):
-            monkeypatch.delenv(k, raising=False)
-        monkeypatch.setenv(env, value)
-        _, _, got[value if env == ENV_ASYNC else 'fp32_dumps'] = step()
-        assert seen[-1].split is split and seen[-1].sweep is True, (env, value)
+    monkeypatch.setattr(tr, 'split_dumps', False)
+    _, _, fp32_dumps = step()
+    assert seen[-1].split is False and seen[-1].sweep is True
     close = lambda a, b, tol: float((a - b).abs().max()) <= tol * float(b.abs().max())          # noqa: E731
     for n in tr.names:
-        if n.endswith('.weight'):
-            assert torch.equal(got['0'][n], got['1'][n]), n
-        for form in ('1', '2', '0'):
-            assert close(got[form][n], got['3'][n], 1e-5), (form, n)
-        assert close(got['fp32_dumps'][n], got['3'][n], 2e-4), n
+        assert close(fp32_dumps[n], grads[n], 2e-4), n

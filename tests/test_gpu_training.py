@@ -404,48 +404,36 @@ def test_training_step_at_benched_c5_shape_matches_reference(dev, precision):
             assert np.abs(got.reshape(-1)[::53] - g['grad_stride53.' + name]).max() < tol * gmax, name
 
 
-def test_weight_gradient_routes_agree(dev, monkeypatch):
-    """r4: the backward pass has four routes to the eleven 64 -> 64 weight gradients -- split-row dumps + global_load_lds kernel
-    (on 16x16x32 MFMAs: the default; on 32x32x16), its eight-wave form, split rows on the register-staged kernel, fp32 dumps -- and the first three feed the MFMAs the
-    SAME fp16 hi / lo halves: the register-staged and the four-wave kernel sum them in the same order (bitwise equal weight
-    gradients), the eight-wave form groups a tile's K-steps differently (1e-5); the fp32-dump route differs only in the leaky-ReLU
-    mask of activations below 2^-25 and in the bias sums' order.  All of them against the reference golden.
+def test_weight_gradient_routes_agree(dev):
+    """The sweep route keeps its activations for the eleven 64 -> 64 weight gradients as split rows or, with
+    `TrainEngine.split_dumps = False`, as fp32 dumps; the two differ only in the leaky-ReLU mask of activations below 2^-25
+    and in the bias sums' order.  Both steps against the reference golden's loss, each other at 2e-4 x gmax, the default
+    against the golden's gradients at 2e-3 x gmax.
 
     WHAT RUNS HERE, on a 256-CU device: at 8 x 2000 the launch cuts every waveform into 8 segments of 250 + 76 + 4 = 330 stream
     rows, below the 384 the two-pass sweep kernel needs, so stof_train_sweep_split answers STOF_ERR_UNSUPPORTED and the step runs
-    the r3 sweep kernel with fp32 dumps and stof_train_wgrad_batch on fp32 operands under EVERY one of the five settings: the
-    "routes" above are one route there, and the comparisons below compare it with itself.  They stay as a check that the
-    switches are harmless at this shape.  The routes themselves -- each kernel form on split rows, and the whole step with these
-    switches at shapes where the engine does take split dumps -- are tested in tests/test_gpu_split_route.py
-    (test_wgrad_batch_split_second_tile_exact, test_whole_step_on_the_split_route)."""
+    the r3 sweep kernel with fp32 dumps and stof_train_wgrad_batch on fp32 operands under BOTH settings: the comparison below
+    compares one route with itself.  It stays as a check that the attribute is harmless at this shape.  The same comparison at
+    shapes where the engine does take split dumps is tests/test_gpu_split_route.py::test_whole_step_on_the_split_route, and
+    the weight-gradient kernels on split rows are test_wgrad_batch_split_second_tile_exact there."""
     from conftest import golden
     g = golden('f8_training_c5')
     frame = torch.from_numpy(synth.synth_echo(8, 2000, seed=3008)).to(dev)
     gt = torch.from_numpy(g['gt_true']).to(dev)
-    routes = {'async4': {'STOF_TRAIN_WGRAD_ASYNC': '1'}, 'async8': {'STOF_TRAIN_WGRAD_ASYNC': '2'}, 'async16': {'STOF_TRAIN_WGRAD_ASYNC': '3'},
-              'split_regs': {'STOF_TRAIN_WGRAD_ASYNC': '0'}, 'fp32_dumps': {'STOF_TRAIN_SPLIT_DUMPS': '0'}}
     got = {}
-    for name, env in routes.items():
-        for k in ('STOF_TRAIN_WGRAD_ASYNC', 'STOF_TRAIN_SPLIT_DUMPS'):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+    for name, split_dumps in (('default', True), ('fp32_dumps', False)):
         sd, m, tr = make(dev, 10, 80, seed=3008, precision='f16x3')
+        assert tr.split_dumps is True
+        tr.split_dumps = split_dumps
         loss, pred = tr.forward_backward(frame, gt)
         got[name] = {n: tr.g[n].detach().clone() for n in tr.names}
         assert abs(float(loss) - float(g['loss'])) < 2e-6 * float(g['loss'])
-    for name in ('async8', 'async16', 'split_regs'):
-        for n in got['async4']:
-            if n.endswith('.weight') and name == 'split_regs':     # same tiles per partial, same order inside a tile
-                assert torch.equal(got[name][n], got['async4'][n]), (name, n)
-            else:                                                  # async8 / async16 group a tile's K-steps differently; bias sums differ in order
-                assert float((got[name][n] - got['async4'][n]).abs().max()) <= 1e-5 * float(got['async4'][n].abs().max()) + 1e-12, (name, n)
-    for n in got['async4']:
+    for n in got['default']:
         gmax = float(g['gmax.' + n])
-        assert float((got['fp32_dumps'][n] - got['async4'][n]).abs().max()) < 2e-4 * gmax, n
+        assert float((got['fp32_dumps'][n] - got['default'][n]).abs().max()) < 2e-4 * gmax, n
         ref = g['grad.' + n] if 'grad.' + n in g.files else None
         if ref is not None:
-            assert np.abs(got['async4'][n].cpu().numpy() - ref).max() < 2e-3 * gmax, n
+            assert np.abs(got['default'][n].cpu().numpy() - ref).max() < 2e-3 * gmax, n
 
 
 def test_loss_target_matches_reference_blur(dev):
